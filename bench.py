@@ -16,11 +16,18 @@ Workload at N=1: BASELINE.json config "battle 1000x1000, 2x500k" in the feasible
 SURVEY.md 8d: 2 x 400k agents placed by the reference's `random` method (2 x 500k does not fit the 996,004
 placeable cells).
 
-The JSON line also carries
+A plain run does only what the headline needs: it builds the world, preheats and warms up, times exactly K steps
+(one region), writes the outputs if --dump-outputs is given and prints the line.  With --full the line also carries
   roofline     : the observation-render kernel, algorithmic bytes (4*(VH*VW*C + F) per rendered agent) over its
                  HIP-event-timed duration on the engine's stream, against the 8 TB/s HBM peak;
   cpu_baseline : the compiled reference engine (oracle/_ref, kind "reference") or the CPU restatement (kind
-                 "port") timed on this host's cores on a bounded sample of the same workload (rank 0, N=1 only).
+                 "port") timed on this host's cores on a bounded sample of the same workload (rank 0, N=1 only);
+and the median of --repeats regions (default 5), the regions without the preheat, the phase breakdown and the extras
+(other sizes, configurations and precisions; for N > 1 the config-4 gather).
+
+--dump-outputs DIR writes what the timed path handed its caller in its last timed step (rank 0's replica), as float32
+.npy files: g<G>_reward (every agent of acting group G), g<G>_view_rows and g<G>_feature_rows (the observation rows of
+a fixed, seeded sample of that group's agents, the same rows for both, as many as fit in DUMP_BYTES in all).
 """
 import argparse
 import json
@@ -38,6 +45,25 @@ WORKLOAD = "battle 1000x1000, 2x400k agents, random placement (C3(i): 2x500k doe
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec
 PREHEAT_MS = 40.0       # per region, before the warm-up steps: back-to-back renders of step 0's observation (see measure)
 EVENT_EVERY = 4         # timed region: the dominant kernel's launches of every 4th step carry HIP events (see measure / one_step)
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs: bytes of array data written in all
+
+
+def last_step_outputs(torch, last, budget=DUMP_BYTES):
+    """--dump-outputs: `last` maps every acting group g to (view tensor, feature tensor, reward tensor, n) of the last timed step.
+    Every reward; the view and feature rows of a fixed, seeded sample of the n agents (rows in ascending order), sized to the budget."""
+    import numpy as np
+    reward_bytes = sum(4 * n for _, _, _, n in last.values())
+    row_bytes = sum(4 * (v[0].numel() + f[0].numel()) for v, f, _, _ in last.values())
+    k_max = max(0, int(budget - reward_bytes) // max(1, row_bytes))
+    out = {}
+    for g, (view, feat, reward, n) in sorted(last.items()):
+        k = min(n, k_max)
+        rows = np.sort(np.random.RandomState(1000 + g).choice(n, k, replace=False)) if k < n else np.arange(n)
+        idx = torch.from_numpy(rows).to(view.device)
+        out["g%d_view_rows" % g] = view[:n].index_select(0, idx).float().cpu().numpy()
+        out["g%d_feature_rows" % g] = feat[:n].index_select(0, idx).float().cpu().numpy()
+        out["g%d_reward" % g] = reward[:n].float().cpu().numpy()
+    return out
 
 
 def cpu_baseline_worker(args):
@@ -509,7 +535,12 @@ def main():
                     help="bf16: render the observations as the policy kernels' bf16 cells (env_get_observation_device_bf16, 8 x bf16 per window "
                          "cell) -- a secondary reading; the headline stays on the reference's float32 tensors")
     ap.add_argument("--extra-timeout", type=int, default=180, help="N > 1: seconds the config-4 gather extra may take before the line is printed without it")
-    ap.add_argument("--repeats", type=int, default=5, help="identical timed regions of --steps steps; the median one is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and phase breakdown, --repeats regions, the regions without the preheat, "
+                         "the CPU baseline, the extras (other sizes, configurations, precisions; for N > 1 the config-4 gather)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs (rewards; view / feature rows of a seeded sample of agents) as DIR/<name>.npy, float32")
+    ap.add_argument("--repeats", type=int, default=None, help="identical timed regions of --steps steps; the median one is reported (default: 1, with --full 5)")
     ap.add_argument("--event-every", type=int, default=EVENT_EVERY, help="timed region: HIP events around the render launches of every N-th step (1: all)")
     ap.add_argument("--preheat-ms", type=float, default=PREHEAT_MS,
                     help="milliseconds of untimed render launches before the warm-up steps of every region: the device's sustained state (see measure); 0: none")
@@ -526,6 +557,8 @@ def main():
                     help="with --gather: after the timed region every rank digests its own rendered rows and the shards it received; "
                          "rank 0 prints which shards were bit-identical to the peer's own tensor (config.gather_detail.verified)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.cpu_baseline_worker:
         return cpu_baseline_worker(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -569,8 +602,9 @@ def main():
             data_group["g"] = dist.new_group(backend="nccl")      # (every rank passes here together: measure() is called in lockstep)
         return data_group["g"]
 
-    def measure(workload, map_size, agents, steps, warmup, profile, gather="none", seed=12345 + rank, check_gather=False, preheat_ms=None):
-        """K timed steps of `workload`; returns the fields of the bench line that depend on the run"""
+    def measure(workload, map_size, agents, steps, warmup, profile, gather="none", seed=12345 + rank, check_gather=False, preheat_ms=None, dump=False):
+        """K timed steps of `workload`; returns the fields of the bench line that depend on the run (dump: and, as "outputs", what the
+        last timed step handed its caller -- see last_step_outputs)"""
         from magent_amd.builtin.config import _games
         if workload == "test_1m":
             map_size = int((2 * agents * 20) ** 0.5)
@@ -642,6 +676,7 @@ def main():
         torch.cuda.synchronize()
         rendered = {"view": 0, "feat": 0, "launches": 0, "agents": []}
         step_ends = []
+        last = {}     # acting group -> (view, features, rewards, n) of the latest step
 
         sampling = {"on": False}
 
@@ -670,6 +705,7 @@ def main():
                 else:
                     env.get_observation_device(h, view, feats[g])
                 env.set_action_device(h, actions[s % n_sets][g])
+                last[g] = (view, feats[g], rewards[g], n)
                 if gathers:                      # counts now (behind the render, on the side stream); the rows follow below
                     if args.backend == "nccl":
                         gathers[g].launch(view, n, producer_stream=env.stream)
@@ -741,9 +777,11 @@ def main():
         elapsed = time.perf_counter() - t0
         per_step = sorted(b - a for a, b in zip([t0] + step_ends[:-1], step_ends))
         median_ms = per_step[len(per_step) // 2] * 1e3 if per_step else None
+        outputs = last_step_outputs(torch, last) if dump else None     # (before the steps some --full figures play after the region)
 
         res = {"elapsed": elapsed, "agent_steps": agent_steps, "median_ms": median_ms, "n0": n0, "agents_at_end": [env.get_num(h) for h in handles],
-               "host_finished_steps": env.engine_stats()[0], "preheat_launches": preheat_launches, "attack_round_hist": list(env.round_hist()), "cycles_run": total_steps, "roofline": None, "breakdown": {}, "map_size": map_size}
+               "host_finished_steps": env.engine_stats()[0], "preheat_launches": preheat_launches, "attack_round_hist": list(env.round_hist()), "cycles_run": total_steps, "roofline": None, "breakdown": {}, "map_size": map_size,
+               "outputs": outputs}
         sampling["on"] = False
         if profile:
             n_launch, ms = env.profile_read("render")
@@ -861,11 +899,13 @@ def main():
     # The headline: W untimed warm-up steps, then EXACTLY K timed steps between barriers + synchronisations -- done `--repeats` times
     # on identically built worlds (same seed, same actions: the K-step window is the same work every time), and the repeat with
     # the MEDIAN time is the one reported (a 20-step region is ~17 ms: one region moves +-2 % on nothing).  Every repeat's
-    # ms/step is in the line (`repeats_ms_per_step`).
+    # ms/step is in the line (`repeats_ms_per_step`).  A plain run times one region; HIP events (roofline, breakdown) only with --full.
+    profile = args.full and not args.no_profile
+    n_rep = max(1, args.repeats)
     runs = []
-    for rep in range(max(1, args.repeats)):
-        R = measure(args.workload, args.map_size, args.agents, args.steps, args.warmup, not args.no_profile, gather=args.gather,
-                    check_gather=args.check_gather and rep == 0)
+    for rep in range(n_rep):
+        R = measure(args.workload, args.map_size, args.agents, args.steps, args.warmup, profile, gather=args.gather,
+                    check_gather=args.check_gather and rep == 0, dump=bool(args.dump_outputs) and rank == 0 and rep == n_rep - 1)
         e, a = R["elapsed"], R["agent_steps"]
         if world > 1:   # whole-job aggregate over the slowest replica's time
             e = replicas.max_over_replicas(e, device=red_dev)
@@ -876,12 +916,17 @@ def main():
     if args.check_gather and "gather" in runs[0][2] and "verified" in runs[0][2]["gather"]:
         R.setdefault("gather", {})["verified"] = runs[0][2]["gather"]["verified"]
     repeats_ms = [round(r[0] / args.steps * 1e3, 4) for r in runs]
+    if args.dump_outputs and rank == 0:     # (the repeats are the same work: their last steps computed the same arrays)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in sorted(runs[-1][2]["outputs"].items()):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
 
     # ... and the same region WITHOUT the preheat, beside it (ADVICE / VERDICT round 4): what a caller sees whose device was idle a moment
     # ago -- the figure every line of rounds 1-3 carried.  Three regions, the median one; N = 1 only (no barriers involved).
     cold = None
-    if world == 1 and args.preheat_ms > 0 and not args.no_cold:
-        cr = [measure(args.workload, args.map_size, args.agents, args.steps, args.warmup, not args.no_profile, preheat_ms=0.0) for _ in range(3)]
+    if world == 1 and args.full and args.preheat_ms > 0 and not args.no_cold:
+        cr = [measure(args.workload, args.map_size, args.agents, args.steps, args.warmup, profile, preheat_ms=0.0) for _ in range(3)]
         cr.sort(key=lambda r: r["elapsed"])
         c = cr[1]
         cold = {"ms_per_step": c["elapsed"] / args.steps * 1e3, "value": c["agent_steps"] / c["elapsed"], "regions_ms_per_step": [round(r["elapsed"] / args.steps * 1e3, 4) for r in cr],
@@ -907,7 +952,8 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_median": R["median_ms"],
             "repeats": len(runs), "repeats_ms_per_step": repeats_ms,
-            "value_is": "the repeat with the median time of %d identical %d-step regions, each behind %.0f ms of untimed renders (the device's sustained state)" % (len(runs), args.steps, args.preheat_ms),
+            "value_is": ("the repeat with the median time of %d identical %d-step regions, each" % (len(runs), args.steps) if len(runs) > 1 else "one %d-step region" % args.steps) +
+                        " behind %.0f ms of untimed renders (the device's sustained state)" % args.preheat_ms,
             "ms_per_step_no_preheat": cold["ms_per_step"] if cold else None, "no_preheat": cold,
             "higher_is_better": True,
             "scaling": "weak",
@@ -931,13 +977,13 @@ def main():
         }
         if "gather" in R:
             rec["config"]["gather_detail"] = R["gather"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             small = args.map_size * args.map_size <= 250000
             rec["cpu_baseline"] = run_cpu_baseline(args.map_size, args.agents, steps=200 if small else 20) \
                 if args.workload == "battle" else None
         else:
             rec["cpu_baseline"] = None
-        if world == 1 and is_default and not args.no_extras:
+        if world == 1 and is_default and args.full and not args.no_extras:
             # the other readings of "battle 1000x1000 / 1M agents" the survey sanctions, and BASELINE config 2, each a short run
             extra = {}
             try:
@@ -982,7 +1028,7 @@ def main():
             except Exception as e:     # secondary lines never fail the bench
                 extra["error"] = repr(e)
             rec["extra"] = extra
-    if world > 1 and (is_default_workload(args) or args.force_extra) and not args.no_extras:
+    if world > 1 and args.full and (is_default_workload(args) or args.force_extra) and not args.no_extras:
         # north-star configuration 4 on the ranks of this job: gather 500 x 500, 100k agents + 20k food per replica, every replica's
         # observation tensor to every rank each step (counts first, rows sized by count, on a side stream under the step) -- timed
         # without and with the exchange, every gathered shard checked bit for bit against the rows its owner rendered.

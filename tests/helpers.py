@@ -53,6 +53,17 @@ def have_ref():
     return os.path.exists(REF_LIB)
 
 
+def single_threaded_reference():
+    """the compiled reference's attack loop is order-nondeterministic with more than one OpenMP thread.  The
+    OMP_NUM_THREADS=1 of tests/conftest.py only counts if the OpenMP runtime starts after it was set: in a process where something
+    started it earlier, under the host's own OMP_NUM_THREADS, the reference ran multithreaded and its trajectories drifted.  So the
+    calling thread's team size is set through the runtime itself, whenever a world of the reference is made."""
+    import ctypes
+    ref = ctypes.CDLL(REF_LIB)          # (the reference links the OpenMP runtime: its symbols resolve through this handle)
+    ref.omp_set_num_threads(1)
+    assert ref.omp_get_max_threads() == 1
+
+
 _WORLDS = {}
 
 
@@ -79,6 +90,8 @@ def world_on(lib):
     if lib is None or os.path.abspath(lib) == os.path.abspath(PRODUCT_LIB):
         return magent_amd.GridWorld
     key = os.path.abspath(lib)
+    if key == os.path.abspath(REF_LIB):
+        single_threaded_reference()
     if key not in _WORLDS:
         _WORLDS[key] = type("CheckerWorld", (magent_amd.GridWorld,), {"_engine_path": key})
     return _WORLDS[key]

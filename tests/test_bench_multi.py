@@ -78,7 +78,7 @@ def test_a_rank_that_dies_in_the_extra_costs_the_extra_not_the_line():
     command succeeds"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--repeats", "1", "--map-size", "200", "--agents", "6000", "--force-extra", "--fault", "kill-rank-1-in-extra"],
+                        "--repeats", "1", "--map-size", "200", "--agents", "6000", "--full", "--force-extra", "--fault", "kill-rank-1-in-extra"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     assert p.returncode == 0 and len(lines) == 1, (p.returncode, p.stdout[-1500:], p.stderr[-3000:])
@@ -93,7 +93,7 @@ def test_two_ranks_share_the_gpu_and_exchange_their_observations():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--gather", "obs",
                         "--check-gather", "--steps", "3", "--warmup", "1", "--map-size", "200", "--agents", "6000",
-                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
     rec = json.loads(line)
@@ -123,14 +123,14 @@ def test_two_ranks_rccl_when_two_gpus():
 
 @pytest.mark.gpu
 def test_default_multi_rank_line_carries_the_c4_gather_extra():
-    """`bench.py --gpus 2` with nothing else but the dry-run backend -- what the driver's N > 1 command produces: the replicas
+    """`bench.py --gpus 2 --full` with nothing else but the dry-run backend -- what the driver's N > 1 command produces with --full: the replicas
     headline on the default workload (no gather), and behind it `extra.c4_gather_rccl`: BASELINE config 4 on the job's ranks
     (gather 500 x 500, 100k agents + 20k food per replica), timed without and with the exchange of every replica's observation
     tensor, the exchange's own duration, bytes per peer and GB/s per link against the xGMI link peak, every gathered shard verified
     bit for bit against the rows its owner rendered"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1",
-                        "--repeats", "1"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--repeats", "1", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["config"]["gather"] == "none" and rec["config"]["agents_at_start"] == [400000, 400000]
@@ -142,7 +142,7 @@ def test_default_multi_rank_line_carries_the_c4_gather_extra():
 
 @pytest.mark.gpu
 def test_default_eight_rank_command_as_a_dry_run():
-    """THE command the driver runs for the 8-GPU scaling point -- `python bench.py --gpus 8` with its default steps and warm-up, nothing else but
+    """THE command the driver runs for the 8-GPU scaling point, with --full -- `python bench.py --gpus 8 --full` with its default steps and warm-up, nothing else but
     the dry-run backend (8 ranks share this box's one GPU, so the process groups are gloo; everything else is the N = 8 path: eight engine
     replicas, the barrier + max-over-ranks timing, the lazily created gather group behind a watchdog, extra.c4_gather_rccl with seven peers
     per rank).  Must finish within two minutes, print exactly ONE JSON line, and that line must carry what the scaling report reads: the
@@ -150,7 +150,7 @@ def test_default_eight_rank_command_as_a_dry_run():
     import time
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo"], capture_output=True, text=True, timeout=600,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--full"], capture_output=True, text=True, timeout=600,
                        env=env, cwd=ROOT)
     wall = time.time() - t0
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

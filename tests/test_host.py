@@ -238,5 +238,5 @@ def test_bench_command_line_parses_without_a_gpu():
     CPU box -- the flags the driver passes (--gpus, --steps, --warmup) and the ones the profiles quote"""
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--repeats", "--event-every", "--preheat-ms", "--backend", "--gather", "--no-extras"):
+    for flag in ("--gpus", "--steps", "--warmup", "--repeats", "--event-every", "--preheat-ms", "--backend", "--gather", "--no-extras", "--full", "--dump-outputs"):
         assert flag in p.stdout, flag

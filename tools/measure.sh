@@ -9,14 +9,14 @@
 #   callers   tests/test_callers.py -m gpu: the reference's own scripts on the HIP engine (figures -> gpurun_out/callers.json)
 #   fuzz      a slice of every fuzz generator on every step driver
 #   line      one bench line without extras / CPU baseline         -> line.json
-#   full      the driver's default command (extras, CPU baseline)  -> full.json
+#   full      bench.py --full (extras, CPU baseline)               -> full.json
 #   stats     rocprofv3 --kernel-trace --stats of a short run      -> stats/bench_kernel_stats.csv + a table
 #   bytes     FETCH_SIZE / WRITE_SIZE / TCC_EA0_RDREQ / TCC_EA0_WRREQ passes (separate --pmc runs) -> bytes.json + a table
 #   pmc       the full counter set of tools/step_pmc.sh
 #   ab        `line` once per MAGENT_TUNE setting of AB="set1;set2;..." ("-" = the defaults)   -> ab_<n>.json, one row each
 #   timeline  the launches of one step in order, from the trace `stats` wrote (tools/step_timeline.py)
-#   default   the driver's default command timed end to end (wall seconds, return code)                       -> full.json
-#   n8        the default N = 8 command as a dry run over gloo on this one GPU + tests/test_bench_multi.py      -> n8_gloo.json
+#   default   bench.py --full timed end to end (wall seconds, return code)                                    -> full.json
+#   n8        the N = 8 command with --full as a dry run over gloo on one GPU + tests/test_bench_multi.py       -> n8_gloo.json
 #   probes    tools/probe/*.hip + tools/render_locality.py (how stores and window reads behave on this part)
 # Environment: K (pytest -k of `parity`), AB (settings of `ab`), FUZZ_FROM / FUZZ_N (first seed and seeds per generator of `fuzz`; default 0 / as listed)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=${1:-m}; JOBS=${2:-line}; shift; shift
@@ -24,7 +24,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; TAG=${1:-m}; JOBS=${2:-
 ARGS="$*"
 O=$R/gpurun_out/$TAG; mkdir -p $O
 export OMP_NUM_THREADS=${OMP_NUM_THREADS:-1}
-short="--steps 8 --warmup 2 --repeats 1 --no-cpu-baseline --no-extras --no-cold"
+short="--full --steps 8 --warmup 2 --repeats 1 --no-cpu-baseline --no-extras --no-cold"
 
 table() {   # kernel table of a rocprofv3 --stats csv
 python - "$1" <<'PY'
@@ -61,7 +61,7 @@ for job in ${JOBS//,/ }; do
               run FUZZ_PLAIN=1 FUZZ_BATCH=3 MAGENT_TUNE=batch_pipe_min=1,attack_pairs=1 python tools/fuzz_parity.py oracle hip $(s 400) $(s 700)
               run FUZZ_PLAIN=1 FUZZ_BATCH=4 MAGENT_TUNE=batch_pipe_min=1,attack_pairs=0 python tools/fuzz_parity.py oracle hip $(s 700) $(s 900)
               run FUZZ_BATCH=3 FUZZ_TURN=1 python tools/fuzz_parity.py oracle hip $(s 0) $(s 200)) 2>&1 | tee $O/fuzz.log ;;
-    line)    (cd /tmp && export TMPDIR=/tmp && timeout 900 python $R/bench.py --no-cpu-baseline --no-extras --no-cold $ARGS > $O/line.json 2> $O/line.err)
+    line)    (cd /tmp && export TMPDIR=/tmp && timeout 900 python $R/bench.py --full --no-cpu-baseline --no-extras --no-cold $ARGS > $O/line.json 2> $O/line.err)
              python - $O/line.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -72,7 +72,7 @@ print("breakdown:", d["breakdown"])
 print("host-finished steps", d["config"]["steps_finished_by_host_driver"], " rounds", d["config"]["attack_round_hist"], " agents", d["config"]["agents_at_start"], "->", d["config"]["agents_at_end"])
 PY
              ;;
-    full)    (cd /tmp && export TMPDIR=/tmp && timeout 1500 python $R/bench.py $ARGS > $O/full.json 2> $O/full.err); tail -c 600 $O/full.json ;;
+    full)    (cd /tmp && export TMPDIR=/tmp && timeout 1500 python $R/bench.py --full $ARGS > $O/full.json 2> $O/full.err); tail -c 600 $O/full.json ;;
     stats)   (cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python $R/bench.py $short $ARGS > $O/stats.log 2>&1)
              table $O/stats/bench_kernel_stats.csv ;;
     bytes)   for c in FETCH_SIZE WRITE_SIZE TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum; do
@@ -83,7 +83,7 @@ PY
     ab)      i=0; IFS=';' read -ra SETS <<< "${AB:--}"
              for t in "${SETS[@]}"; do
                [ "$t" = "-" ] && t=""
-               (cd /tmp && export TMPDIR=/tmp && MAGENT_TUNE="$t" timeout 900 python $R/bench.py --no-cpu-baseline --no-extras --no-cold $ARGS > $O/ab_$i.json 2> $O/ab_$i.err)
+               (cd /tmp && export TMPDIR=/tmp && MAGENT_TUNE="$t" timeout 900 python $R/bench.py --full --no-cpu-baseline --no-extras --no-cold $ARGS > $O/ab_$i.json 2> $O/ab_$i.err)
                python - $O/ab_$i.json "$t" <<'PY'
 import json, sys
 try:
@@ -100,11 +100,11 @@ PY
     default) python - <<PY
 import subprocess, time, json
 t0 = time.time()
-p = subprocess.run(["python", "$R/bench.py"] + "$ARGS".split(), capture_output=True, text=True, timeout=1500, cwd="/tmp")
+p = subprocess.run(["python", "$R/bench.py", "--full"] + "$ARGS".split(), capture_output=True, text=True, timeout=1500, cwd="/tmp")
 dt = time.time() - t0
 open("$O/full.json", "w").write(p.stdout); open("$O/full.err", "w").write(p.stderr)
 rec = json.loads([l for l in p.stdout.splitlines() if l.startswith('{"metric"')][-1])
-print("default bench.py: wall %.1f s rc %d" % (dt, p.returncode))
+print("bench.py --full: wall %.1f s rc %d" % (dt, p.returncode))
 print("%.4e  %.4f ms  no_preheat %s  frac %s" % (rec["value"], rec["ms_per_step"], rec.get("ms_per_step_no_preheat"), rec["roofline"]["frac"]))
 print("cpu:", rec["cpu_baseline"])
 e = rec.get("extra", {})
@@ -116,11 +116,11 @@ PY
              python - <<PY
 import subprocess, time, json
 t0 = time.time()
-p = subprocess.run(["python", "$R/bench.py", "--gpus", "8", "--backend", "gloo", "--extra-timeout", "900"], capture_output=True, text=True, timeout=1500, cwd="/tmp")
+p = subprocess.run(["python", "$R/bench.py", "--gpus", "8", "--backend", "gloo", "--full", "--extra-timeout", "900"], capture_output=True, text=True, timeout=1500, cwd="/tmp")
 dt = time.time() - t0
 lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]
 rec = json.loads(lines[-1])
-rec["dry_run"] = {"command": "python bench.py --gpus 8 --backend gloo", "wall_seconds": round(dt, 1), "returncode": p.returncode, "json_lines": len(lines),
+rec["dry_run"] = {"command": "python bench.py --gpus 8 --backend gloo --full", "wall_seconds": round(dt, 1), "returncode": p.returncode, "json_lines": len(lines),
                   "note": "8 ranks share ONE MI355X over gloo: the driver's default N = 8 command end to end (headline on config 3 per rank, then extra.c4_gather_rccl with every shard verified); a dry run of the code path and its footprint, not a measurement of xGMI"}
 json.dump(rec, open("$O/n8_gloo.json", "w"), indent=1)
 print("wall %.1f s, rc %d, %d line(s); value %.3e; extra verified %s" % (dt, p.returncode, len(lines), rec["value"], rec["extra"]["c4_gather_rccl"].get("verified")))
