@@ -11,6 +11,7 @@
  * env_get_info("num") x the *_space infos; the engine owns the opaque EnvHandle until env_delete_game.
  * PART 1 buffers are HOST memory; each call is synchronous (outputs valid on return).
  * PART 2 is additive: the same operations on DEVICE pointers, asynchronous on the environment's HIP stream.
+ * PART 3 holds the reference's three rule-based actors (host, runtime_api.h:64-73) and their device entry.
  *
  * Errors: like the reference (LOG(FATAL) -> std::terminate under ctypes, utility.h:77-80) an invalid
  * argument or an unsupported feature prints "magent-amd FATAL: ..." to stderr and aborts; nothing returns
@@ -163,6 +164,44 @@ int env_streams_many(EnvHandle *games, int n_env, void **out);
  * the number of recorded launches and their total duration in milliseconds, and resets the counters. */
 int env_profile_enable(EnvHandle game, int on);
 int env_profile_read(EnvHandle game, const char *name, int *n_launches, float *total_ms);
+
+/* ---------------------------------------------------------------------------------------------------
+ * PART 3 -- rule-based actors (reference src/temp_c_booster.cc; magent_amd/csrc/actors.hip)
+ * ------------------------------------------------------------------------------------------------- */
+
+/* runtime_api.h:64-73, with the reference's exact signatures and, unlike the reference, as C symbols.  HOST buffers:
+ * obs_buf = view float[n][height][width][n_channel], feature_buf / hp_buf = feature float[n][feature_size], act_buf = int32[n],
+ * view2attack_buf = int32[height][width].  One sequential loop over the agents in ascending order, drawing from libc's own
+ * random() / rand() at exactly the reference's points: for the same libc state, the actions and the state afterwards equal the
+ * reference's run on one thread.  Two definitions of the product: rush_prey's threshold test reads feature_buf[i], the i-th
+ * float of the flattened feature array (as the reference does); gather's minimap step with no minimap cell -- a division
+ * by zero in the reference -- draws rand() % attack_base. */
+void runaway_infer_action(float *obs_buf, float *feature_buf, int n, int height, int width, int n_channel,
+                          int attack_base, int *act_buf, int away_channel, int move_back);
+void rush_prey_infer_action(float *obs_buf, float *feature_buf, int n, int height, int width, int n_channel,
+                            int *act_buf, int attack_channel, int attack_base,
+                            int *view2attack_buf, float threshold);
+void gather_infer_action(float *obs_buf, float *hp_buf, int n, int height, int width, int n_channel,
+                         int *act_buf, int attack_base, int *view2attack_buf);
+
+/* The same three policies on DEVICE observations. */
+enum { MAGENT_ACTOR_RUNAWAY = 0, MAGENT_ACTOR_RUSH_PREY = 1, MAGENT_ACTOR_GATHER = 2 };
+typedef struct MagentActorArgs {
+    int kind;                       /* MAGENT_ACTOR_* */
+    int n, height, width, n_channel;
+    int attack_base;
+    int channel;                    /* runaway: away_channel; rush_prey: attack_channel; gather: unused (channels 3, 4, 6) */
+    int move_back;                  /* runaway */
+    float threshold;                /* rush_prey */
+    unsigned long long seed, counter;   /* the device's draws: DESIGN.md 3.16 */
+} MagentActorArgs;
+/* view float[n][height][width][n_channel], feature float[n][feature_size], view2attack int32[height * width] (unused by runaway),
+ * actions int32[n], drew uint8[n] or NULL: all DEVICE pointers.  Enqueued on `stream` (a hipStream_t; NULL = the null stream);
+ * no synchronisation, no allocation; n == 0 does nothing.  Every agent whose reference action involves no draw gets exactly the
+ * reference's action and drew[i] = 0; an agent whose action comes from a draw gets drew[i] = 1 and an action uniform over the set
+ * the reference draws from, drawn from a stateless stream of (seed, counter, agent, slot) instead of libc's state. */
+int actor_infer_action_device(const MagentActorArgs *args, const float *view, const float *feature, const int *view2attack,
+                              int *actions, unsigned char *drew, void *stream);
 
 #ifdef __cplusplus
 }

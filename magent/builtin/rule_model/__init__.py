@@ -1,3 +1,3 @@
-from magent_amd.builtin.rule_model import RandomActor
+from magent_amd.builtin.rule_model import RandomActor, RunawayPrey, RushGatherer, RushPredator
 
-__all__ = ["RandomActor"]
+__all__ = ["RandomActor", "RushPredator", "RunawayPrey", "RushGatherer"]

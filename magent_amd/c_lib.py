@@ -64,6 +64,14 @@ POLICY_ABI = [
     ("policy_dqn_f32_act_bytes", [_vp, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_dqn_infer_f32", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
 ]
+# include/magent_runtime_api.h PART 3, the rule-based actors: (name, restype, argtypes).  A table of its own, bound only where
+# the library exports it (the CPU checkers under oracle/ do not; `has_actor_api` says whether this one does).
+ACTOR_ABI = [
+    ("runaway_infer_action", None, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    ("rush_prey_infer_action", None, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _c.c_float]),
+    ("gather_infer_action", None, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    ("actor_infer_action_device", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+]
 
 _cache = {}
 _lock = __import__("threading").Lock()
@@ -109,5 +117,12 @@ def _load(path=None):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    lib.has_actor_api = True
+    for name, restype, argtypes in ACTOR_ABI:
+        fn = getattr(lib, name, None)
+        if fn is None:
+            lib.has_actor_api = False
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
     _cache[path] = lib
     return lib

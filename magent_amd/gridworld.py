@@ -80,6 +80,7 @@ class GridWorld(object):
             config = _builtin_config(config, **kwargs)
 
         self.game = ctypes.c_void_p()
+        self._channel_modes = {"food_mode": False, "minimap_mode": False}
         self._num = ctypes.c_int32(0)
         self._num_ref = ctypes.byref(self._num)       # (get_num's out-parameter; one environment is driven by one thread at a time)
         L.env_new_game(ctypes.byref(self.game), b"GridWorld")
@@ -128,6 +129,8 @@ class GridWorld(object):
     def _config(self, key, kind, val):
         """env_config_game takes a void* whose pointee type depends on the key (GridWorld.cc:120-149); the ctypes
         object is held in a local until the call returns"""
+        if key in ("food_mode", "minimap_mode"):
+            self._channel_modes[key] = bool(val)       # (get_channel's layout)
         if kind is int:
             box = ctypes.c_int(val)
         elif kind is bool:
@@ -309,6 +312,18 @@ class GridWorld(object):
         table = self._info(g, b"view2attack", np.empty(self.view_space[g][:2], dtype=np.int32))
         base = self._info(g, b"attack_base", np.zeros(1, dtype=np.int32))
         return int(base[0]), table
+
+    def get_channel(self, handle, observer=None):
+        """-> the first observation channel of `handle`'s layers in `observer`'s view (the reference's actors call it; its GridWorld
+        does not define it).  The layout of GridWorld.cc:897-924: wall (and food with food_mode) first, then every group's
+        (has, hp[, minimap]) layers, the observer's own group first and the others cyclically after it.  observer=None: the
+        absolute position, group2channel(handle)."""
+        g = _gid(handle)
+        base = 1 + self._channel_modes["food_mode"]
+        scale = 2 + self._channel_modes["minimap_mode"]
+        if observer is None:
+            return base + g * scale
+        return base + (g - _gid(observer)) % len(self.group_handles) * scale
 
     def get_global_minimap(self, height, width):
         buf = np.empty((height, width, len(self.group_handles)), dtype=np.float32)
