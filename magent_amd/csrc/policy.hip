@@ -67,17 +67,20 @@ struct ConvArgs {
     long long *stamps;     // STAMPS instantiation (MAGENT_TUNE policy_stamps=1): per workgroup, cycles spent in each phase
 };
 
-// relu and round two f32 to a bf16 pair: v_cvt_pk_bf16_f32, then v_pk_max_i16 against 0 -- a negative bf16 is a negative int16, and
-// rounding never changes a sign (-0 becomes +0), so max(int16(round(x)), 0) == round(max(x, 0)) bit for bit.  Two instructions per
-// pair; `(__bf16)fmaxf(x, 0)` is five (two v_max_f32 each -- one quiets NaNs -- and the conversion).
+// relu and round two f32 to a bf16 pair: v_maximum3_f32 per value (IEEE 754-2019 maximum: a NaN stays a NaN, as in torch.relu; -0 gives
+// +0), then v_cvt_pk_bf16_f32 (round to nearest even; a NaN stays a NaN -- MI355X_MICROARCH.md).  Three instructions per pair.  (Until
+// the non-finite contract, DESIGN.md 3.15, the relu was v_pk_max_i16 against 0 on the rounded pair: two instructions, but a NaN with its sign
+// bit set -- the reference's 0/0 of an empty group's minimap -- is a negative int16 and came out as 0; `fmaxf` makes any NaN a 0.)
 __device__ __forceinline__ unsigned relu_bf16x2(float a, float b) {
     typedef __attribute__((ext_vector_type(2))) float f32x2;
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    typedef __attribute__((ext_vector_type(2))) short s16x2;
-    const f32x2 v = {a, b};
-    s16x2 t = __builtin_bit_cast(s16x2, __builtin_convertvector(v, bf16x2));
-    t = __builtin_elementwise_max(t, (s16x2)(0));
-    return __builtin_bit_cast(unsigned, t);
+    const f32x2 v = {__builtin_elementwise_maximum(a, 0.0f), __builtin_elementwise_maximum(b, 0.0f)};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+// torch.argmax's order of a Q row: a NaN above everything (the first NaN wins), then the larger value, the lower index among equals.  Does
+// (v, o) come before (best, arg)?
+__device__ __forceinline__ bool q_before(float v, int o, float best, int arg) {
+    return v != v ? (best == best || o < arg) : (best == best && (v > best || (v == best && o < arg)));
 }
 __device__ __forceinline__ bf16x8 relu_bf16x8(const f32x16 &acc, int base) {
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -517,24 +520,32 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
 #pragma unroll 4
         for (int s = 16; s < 32; s++) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s_wh[s * 64 + l], s_hid[hid_at(hagent, 2 * (s - 16) + g)], h, 0, 0, 0);
         const int agent = hagent;
-        // lane (agent, g) holds outputs ch_of(g, r); its partner lane ^ 32 the other sixteen
-        float best = -INFINITY, sum = 0.0f, value = 0.0f;
-        int arg = 0x7FFFFFFF;
+        // lane (agent, g) holds outputs ch_of(g, r); its partner lane ^ 32 the other sixteen.  The action is the argmax of the Q row
+        // itself, h + shift, in torch.argmax's order (q_before): a NaN reaches the row, then its first NaN is chosen, as the PyTorch path
+        // chooses it; every action lies in [0, n_action) whatever the input
+        float sum = 0.0f, value = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int o = ch_of(g, r);
-            if (o < A.n_action) { sum += h[r]; if (h[r] > best || (h[r] == best && o < arg)) { best = h[r]; arg = o; } }
+            if (o < A.n_action) sum += h[r];
             if (o == A.n_action) value = h[r];
+        }
+        sum += __shfl_xor(sum, 32);
+        value += __shfl_xor(value, 32);
+        const float shift = value + A.value_bias - sum / (float)A.n_action;
+        float best = -INFINITY;
+        int arg = A.n_action;         // (not an action: every output of the row comes before it)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = ch_of(g, r);
+            if (o < A.n_action && q_before(h[r] + shift, o, best, arg)) { best = h[r] + shift; arg = o; }
         }
         const float obest = __shfl_xor(best, 32);
         const int oarg = __shfl_xor(arg, 32);
-        sum += __shfl_xor(sum, 32);
-        value += __shfl_xor(value, 32);
-        if (obest > best || (obest == best && oarg < arg)) { best = obest; arg = oarg; }
+        if (q_before(obest, oarg, best, arg)) { best = obest; arg = oarg; }
         if (a0 + agent < A.n) {
-            if (g == 0) A.actions[a0 + agent] = arg;      // argmax Q = argmax advantage: value and mean are per-agent constants
+            if (g == 0) A.actions[a0 + agent] = arg;
             if (A.q) {
-                const float shift = value + A.value_bias - sum / (float)A.n_action;
 #pragma unroll
                 for (int r = 0; r < 16; r++) { const int o = ch_of(g, r); if (o < A.n_action) A.q[(size_t)(a0 + agent) * A.n_action + o] = h[r] + shift; }
             }

@@ -52,8 +52,16 @@ __device__ __forceinline__ f32x16 mfma4(const f32x4 &w, const f32x4 &x, f32x16 a
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[3], x[3], acc, 0, 0, 0);
     return acc;
 }
+// relu that keeps a NaN a NaN, as torch.relu does (fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0, and a poisoned view or a diverged network would
+// then act on finite garbage).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, the cost of the v_max_f32 it replaces; -0 gives +0.
+__device__ __forceinline__ float relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
 __device__ __forceinline__ f32x4 relu4(const f32x16 &acc, int q) {
-    return f32x4{fmaxf(acc[4 * q], 0.0f), fmaxf(acc[4 * q + 1], 0.0f), fmaxf(acc[4 * q + 2], 0.0f), fmaxf(acc[4 * q + 3], 0.0f)};
+    return f32x4{relu(acc[4 * q]), relu(acc[4 * q + 1]), relu(acc[4 * q + 2]), relu(acc[4 * q + 3])};
+}
+// torch.argmax's order of a Q row: a NaN above everything (the first NaN wins), then the larger value, the lower index among equals.  Does
+// (v, o) come before (best, arg)?
+__device__ __forceinline__ bool q_before(float v, int o, float best, int arg) {
+    return v != v ? (best == best || o < arg) : (best == best && (v > best || (v == best && o < arg)));
 }
 
 // conv2's output, dense_view's input: [group of 128 agents][K-chunk of 64 values = two positions][agent][64 values] (as policy.hip's
@@ -296,8 +304,7 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
             const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const f32x4 v = {fmaxf(acc[j][4 * q] + b[0], 0.0f), fmaxf(acc[j][4 * q + 1] + b[1], 0.0f), fmaxf(acc[j][4 * q + 2] + b[2], 0.0f),
-                                 fmaxf(acc[j][4 * q + 3] + b[3], 0.0f)};
+                const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
                 s_hid[hid_slot(32 * j + r32, 8 * w + 2 * q + g)] = v;
             }
         }
@@ -334,24 +341,32 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
     __syncthreads();
     head_half(1);
     if (w < 4) {
-        // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen
-        float best = -INFINITY, sum = 0.0f, value = 0.0f;
-        int arg = 0x7FFFFFFF;
+        // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen.  The action is the argmax of the
+        // Q row itself, h + shift, in torch.argmax's order (q_before): a NaN anywhere in the network reaches the row, and then its first NaN
+        // is chosen, as the PyTorch path chooses it; every action lies in [0, n_action) whatever the input
+        float sum = 0.0f, value = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
-            if (o < A.n_action) { sum += h[r]; if (h[r] > best || (h[r] == best && o < arg)) { best = h[r]; arg = o; } }
+            if (o < A.n_action) sum += h[r];
             if (o == A.n_action) value = h[r];
+        }
+        sum += __shfl_xor(sum, 32);
+        value += __shfl_xor(value, 32);
+        const float shift = value + A.value_bias - sum / (float)A.n_action;
+        float best = -INFINITY;
+        int arg = A.n_action;         // (not an action: every output of the row comes before it)
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+            if (o < A.n_action && q_before(h[r] + shift, o, best, arg)) { best = h[r] + shift; arg = o; }
         }
         const float obest = __shfl_xor(best, 32);
         const int oarg = __shfl_xor(arg, 32);
-        sum += __shfl_xor(sum, 32);
-        value += __shfl_xor(value, 32);
-        if (obest > best || (obest == best && oarg < arg)) { best = obest; arg = oarg; }
+        if (q_before(obest, oarg, best, arg)) { best = obest; arg = oarg; }
         if (a0 + hagent < A.n) {
-            if (g == 0) A.actions[a0 + hagent] = arg;      // argmax Q = argmax advantage: value and mean are per-agent constants
+            if (g == 0) A.actions[a0 + hagent] = arg;
             if (A.q) {
-                const float shift = value + A.value_bias - sum / (float)A.n_action;
 #pragma unroll
                 for (int r = 0; r < 16; r++) { const int o = (r & 3) + 8 * (r >> 2) + 4 * g; if (o < A.n_action) A.q[(size_t)(a0 + hagent) * A.n_action + o] = h[r] + shift; }
             }

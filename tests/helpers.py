@@ -1180,3 +1180,86 @@ def scenarios():
                  over={"small": {"damage": 12}}),
     ]
     return {s.name: s for s in S}
+
+
+# ---------------------------------------------------------------------------------------------------- the DQN in float64
+def qnet_tf_params(qnet):
+    """a dueling conv _QNet's parameters in TensorFlow's layout (tf_model/dqn.py:151-189), float64: conv kernels HWIO, dense kernels
+    [in, out] (torch keeps OIHW and [out, in])"""
+    sd = {k: v.detach().cpu().double().numpy() for k, v in qnet.state_dict().items()}
+    return {"conv1/kernel": sd["conv1.weight"].transpose(2, 3, 1, 0), "conv1/bias": sd["conv1.bias"],
+            "conv2/kernel": sd["conv2.weight"].transpose(2, 3, 1, 0), "conv2/bias": sd["conv2.bias"],
+            "dense_view/kernel": sd["dense_view.weight"].T, "dense_view/bias": sd["dense_view.bias"],
+            "dense_emb/kernel": sd["dense_emb.weight"].T, "dense_emb/bias": sd["dense_emb.bias"],
+            "value/kernel": sd["value.weight"].T, "value/bias": sd["value.bias"],
+            "advantage/kernel": sd["advantage.weight"].T}
+
+
+def round_bf16(a):
+    """a rounded to bfloat16 (nearest even; a NaN stays a NaN), returned as float64"""
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(torch.bfloat16).double().numpy()
+
+
+def np_qnet(params, view, feature, use_dueling=True, dtype=np.float64, magnitude=False, bf16=False):
+    """NumPy restatement of the reference network (tf_model/dqn.py:151-189): conv3x3(32) -> conv3x3(32), both VALID, NHWC, relu ->
+    flatten (h, w, c order) -> dense 256 relu || dense 256 relu on the features -> concat -> dueling head (value + advantage(no bias) -
+    mean advantage).  `params` in TensorFlow's layout (qnet_tf_params).
+
+    Computed in `dtype` throughout.  relu is np.maximum(x, 0), which keeps a NaN a NaN, as torch.relu does.
+    magnitude=True: the same network on |weights|, |biases| and |inputs|, with the dueling head's value + adv - mean(adv) taken as a sum
+      of magnitudes -- per entry the scale that float rounding errors of the real network are bounded by (see f32_error_bound).
+    bf16=True: rounded to bfloat16 where policy.hip's kernels round (inputs, weights, conv1's bias -- it rides in the MFMA as a weight --
+      and the activations between layers); the other biases and every sum stay in `dtype`."""
+    mag = np.abs if magnitude else (lambda a: a)
+    rnd = round_bf16 if bf16 else (lambda a: a)
+    relu = (lambda a: a) if magnitude else (lambda a: np.maximum(a, 0))
+    P = {k: mag(np.asarray(v, dtype=np.float64)).astype(dtype) for k, v in params.items()}
+    for k in ("conv1/kernel", "conv1/bias", "conv2/kernel", "dense_view/kernel", "dense_emb/kernel", "value/kernel", "advantage/kernel"):
+        P[k] = rnd(P[k]).astype(dtype)
+
+    def conv_valid(x, k, b):                       # x [N,H,W,C], k [3,3,C,O]
+        n, h, w, c = x.shape
+        out = np.zeros((n, h - 2, w - 2, k.shape[3]), dtype=dtype)
+        for dy in range(3):
+            for dx in range(3):
+                out += np.tensordot(x[:, dy:dy + h - 2, dx:dx + w - 2, :], k[dy, dx], axes=([3], [0])).astype(dtype)
+        return rnd(relu(out + b)).astype(dtype)
+    x = rnd(mag(np.asarray(view, dtype=np.float64))).astype(dtype)
+    f = rnd(mag(np.asarray(feature, dtype=np.float64))).astype(dtype)
+    h1 = conv_valid(x, P["conv1/kernel"], P["conv1/bias"])
+    h2 = conv_valid(h1, P["conv2/kernel"], P["conv2/bias"])
+    flat = h2.reshape(h2.shape[0], -1)
+    h_view = rnd(relu(flat @ P["dense_view/kernel"] + P["dense_view/bias"]))
+    h_emb = rnd(relu(f @ P["dense_emb/kernel"] + P["dense_emb/bias"]))
+    dense = np.concatenate([h_view, h_emb], axis=1).astype(dtype)
+    value = dense @ P["value/kernel"] + P["value/bias"]
+    if not use_dueling:
+        return value
+    adv = dense @ P["advantage/kernel"]
+    if magnitude:
+        return value + adv + adv.mean(axis=1, keepdims=True)
+    return value + adv - adv.mean(axis=1, keepdims=True)
+
+
+def qnet_f64(qnet, view, feature, bf16=False):
+    """(Q, Qmag) of a _QNet on torch / NumPy inputs, float64 (np_qnet)"""
+    p = qnet_tf_params(qnet)
+    v = view.detach().cpu().double().numpy() if hasattr(view, "detach") else np.asarray(view, np.float64)
+    f = feature.detach().cpu().double().numpy() if hasattr(feature, "detach") else np.asarray(feature, np.float64)
+    return np_qnet(p, v, f, bf16=bf16), np_qnet(p, v, f, magnitude=True, bf16=bf16)
+
+
+def f32_error_bound(view_space, feat, n_action):
+    """c of the per-entry bound |Q_f32 - Q_64| <= c * 2^-24 * Qmag of a float32 evaluation of the network, in any summation order.
+
+    A float32 dot product of length K with a bias is within gamma_(K+1) ~ (K + 1) u of the exact one, relative to the same sum of
+    MAGNITUDES (u = 2^-24, Higham's bound for any order -- an MFMA chain, a blocked GEMM, a Winograd-free convolution).  relu is
+    1-Lipschitz and the later layers multiply an earlier layer's error by at most their |weights|, so each layer's error reaches Q
+    within (K_l + 1) u Qmag, Qmag = the network on |weights|, |biases|, |inputs| (np_qnet magnitude=True).  The layers' reduction
+    lengths: conv1 9 x 8 (the kernels pad the channels to 8), conv2 9 x 32, dense_view H2 x W2 x 32 (up to 15 x 15 x 32 = 7200 in the
+    supported region), dense_emb FK = feat rounded up to 8, the head 512; the dueling head adds the value and the mean of n_action
+    advantages (a sum of n_action terms, one division, two additions).  The two hidden halves are parallel paths; both are counted."""
+    h, w, _ = view_space
+    fk = (feat + 7) // 8 * 8
+    return (72 + 1) + (288 + 1) + ((h - 4) * (w - 4) * 32 + 1) + (fk + 1) + 512 + (n_action + 4)

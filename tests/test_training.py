@@ -123,25 +123,9 @@ def test_episodes_buffer_row_lookup_equals_the_search():
 def _np_qnet(params, view, feature, use_dueling=True):
     """NumPy fp32 restatement of the reference network (tf_model/dqn.py:151-189): conv3x3(32) -> conv3x3(32), both VALID, NHWC,
     relu -> flatten (h, w, c order) -> dense 256 relu || dense 256 relu on the features -> concat -> dueling head
-    (value + advantage(no bias) - mean advantage).  Weights in TensorFlow layout: conv kernels HWIO, dense kernels [in, out]."""
-    def conv_valid(x, k, b):                       # x [N,H,W,C], k [3,3,C,O]
-        n, h, w, c = x.shape
-        out = np.zeros((n, h - 2, w - 2, k.shape[3]), dtype=np.float32)
-        for dy in range(3):
-            for dx in range(3):
-                out += np.tensordot(x[:, dy:dy + h - 2, dx:dx + w - 2, :], k[dy, dx], axes=([3], [0])).astype(np.float32)
-        return np.maximum(out + b, 0).astype(np.float32)
-    h1 = conv_valid(view, params["conv1/kernel"], params["conv1/bias"])
-    h2 = conv_valid(h1, params["conv2/kernel"], params["conv2/bias"])
-    flat = h2.reshape(h2.shape[0], -1)
-    h_view = np.maximum(flat @ params["dense_view/kernel"] + params["dense_view/bias"], 0)
-    h_emb = np.maximum(feature @ params["dense_emb/kernel"] + params["dense_emb/bias"], 0)
-    dense = np.concatenate([h_view, h_emb], axis=1).astype(np.float32)
-    if not use_dueling:
-        return dense @ params["value/kernel"] + params["value/bias"]
-    value = dense @ params["value/kernel"] + params["value/bias"]
-    adv = dense @ params["advantage/kernel"]
-    return value + adv - adv.mean(axis=1, keepdims=True)
+    (value + advantage(no bias) - mean advantage).  Weights in TensorFlow layout: conv kernels HWIO, dense kernels [in, out].
+    (helpers.np_qnet, in float32; tests/test_policy_contract.py runs it in float64 against the HIP kernels)"""
+    return H.np_qnet(params, view, feature, use_dueling=use_dueling, dtype=np.float32)
 
 
 def test_dqn_network_is_the_reference_network():
