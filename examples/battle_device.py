@@ -1,6 +1,6 @@
 """A battle played entirely in HBM: observations, policy and actions never leave the GPU.
 
-    python examples/battle_device.py [--map_size 200] [--n 2000] [--steps 100] [--policy random|dqn]
+    python examples/battle_device.py [--map_size 200] [--n 2000] [--steps 100] [--policy random|dqn|drqn]
 
 The loop is the reference's (examples/train_battle.py:61-109: get_observation -> infer_action -> set_action per group,
 step, get_reward, clear_dead); `device_obs=True` makes get_observation return torch tensors on the engine's GPU, and
@@ -15,7 +15,7 @@ import torch  # noqa: E402
 
 import magent_amd  # noqa: E402
 from magent_amd.builtin.rule_model import RandomActor  # noqa: E402
-from magent_amd.builtin.torch_model import DeepQNetwork  # noqa: E402
+from magent_amd.builtin.torch_model import DeepQNetwork, DeepRecurrentQNetwork  # noqa: E402
 
 
 def main():
@@ -23,7 +23,7 @@ def main():
     ap.add_argument("--map_size", type=int, default=200)
     ap.add_argument("--n", type=int, default=2000, help="agents per side")
     ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--policy", choices=["random", "dqn"], default="random")
+    ap.add_argument("--policy", choices=["random", "dqn", "drqn"], default="random")
     ap.add_argument("--infer-dtype", choices=["f32", "bf16"], default="f32", help="bf16: the MFMA inference kernels (magent_amd/csrc/policy.hip)")
     args = ap.parse_args()
 
@@ -38,6 +38,9 @@ def main():
         # --infer-dtype bf16: the forward pass runs on the hand-written MFMA kernels (magent_amd/csrc/policy.hip); they take the views as bf16 cells of
         # 8 channels, which the engine can render directly (2.7 KB per agent instead of 4.7, nothing to convert)
         env.use_bf16_observations(all(m._hip is not None for m in models))
+    elif args.policy == "drqn":
+        # the kernel path (magent_amd/csrc/policy_drqn_f32.hip): the GRU state of every agent id stays in HBM between steps
+        models = [DeepRecurrentQNetwork(env, h, "side%d" % i, memory_size=16) for i, h in enumerate(handles)]
     else:
         models = [RandomActor(env, h, seed=i) for i, h in enumerate(handles)]
 
@@ -46,7 +49,8 @@ def main():
     for step in range(args.steps):
         for h, m in zip(handles, models):
             obs = env.get_observation(h)                       # (view [n, 13, 13, 7] -- or bf16 [n, 13, 13, 8] --, feature [n, 34]) on the GPU
-            acts = m.infer_action(obs, None, policy="e_greedy", eps=0.1)
+            ids = env.get_agent_id(h) if args.policy == "drqn" else None      # (the recurrent states are keyed by agent id)
+            acts = m.infer_action(obs, ids, policy="e_greedy", eps=0.1)
             env.set_action(h, acts)
             agent_steps += env.get_num(h)
         done = env.step()

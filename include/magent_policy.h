@@ -85,6 +85,41 @@ int policy_dqn_f32_act_bytes(const PolicyDqnShape *shape, int n, size_t *bytes);
 int policy_dqn_infer_f32(const PolicyDqnShape *shape, const PolicyDqnWeightsF32 *weights, const float *view, const float *feature, int n,
                          void *act_workspace, int *actions, float *q, void *stream);
 
+/* ---- the deep recurrent Q network's acting step (magent_amd/builtin/torch_model/drqn.py: _RecurrentQNet, one GRU step per agent) in
+ * float32 -- magent_amd/csrc/policy_drqn_f32.hip.  The trunk is the DQN's (the f32 entries above); a GRU(512) cell follows, then the head
+ * over its output h'.  Weights in f32 fragment order:
+ *   gru  : torch's weight_ih_l0 and weight_hh_l0 [3 x 512][512] (gates r, z, n) side by side, K = x's 512 units, then h's 512;
+ *          the three gate tiles of hidden tile T are adjacent: group m, tile T, gate G at [m][3 T + G]                  [128][48][64][4]
+ *   head : K = the 512 state units; dueling: outputs 0..n_action-1 = advantage, output n_action = value; otherwise outputs
+ *          0..n_action-1 = value; the rest zero                                                                       [64][64][4]
+ * gru_bias  float[4][512]: b_ir + b_hr, b_iz + b_hz, b_in, b_hn (the gates' biases; b_hn stays inside the reset gate's product)
+ * gru_bias0 the same for a zero state: W_h* 0 added to each hidden bias (0, or NaN where a row of weight_hh_l0 is not finite, as torch's
+ *           W_h @ 0) -- used when the state table is empty
+ * head_bias float[32]: per output (dueling: the value's bias at n_action, zeros elsewhere) */
+typedef struct {
+    PolicyDqnWeightsF32 trunk;    /* conv1 .. dense_emb and their biases as for policy_dqn_infer_f32; trunk.head and trunk.value_bias are not read */
+    const void *gru;
+    const float *gru_bias, *gru_bias0;
+    const void *head;
+    const float *head_bias;
+    int dueling;
+} PolicyDrqnWeightsF32;
+
+/* 1 if the DRQN kernels take this shape: policy_dqn_f32_supported's region (the state is 512 wide) */
+int policy_drqn_f32_supported(const PolicyDqnShape *shape);
+/* size of the workspace of one call with n agents (the trunk's activations, then the GRU's input float[n][512]) */
+int policy_drqn_f32_workspace_bytes(const PolicyDqnShape *shape, int n, size_t *bytes);
+/* One step of n agents.  ids int[n]: this call's agent ids.  The state table of the previous call: prev_sorted_ids int[count] its ids
+ * sorted ascending (stably: equal ids in that call's order), rows int[count] the row of `states` float[.][512] holding each one's state.
+ * Agent i starts from the row of the LAST entry of prev_sorted_ids equal to ids[i] (the last occurrence of a duplicated id), or from
+ * zeros if there is none; count == 0 is an empty table.  new_states float[n][512]: h' of agent i in row i (must not overlap `states`).
+ * states, new_states and the workspace are 16-byte aligned (a call with one that is not is refused).
+ * actions[i] = torch.argmax of Q row i (a NaN first, then the larger value, then the lower index); q (optional) float[n][n_action].
+ * Enqueues four kernels on `stream` and returns 0, or non-zero if the shape is not supported / a pointer is missing / a launch failed. */
+int policy_drqn_infer_f32(const PolicyDqnShape *shape, const PolicyDrqnWeightsF32 *weights, const float *view, const float *feature, int n,
+                          const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
+                          void *workspace, int *actions, float *q, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

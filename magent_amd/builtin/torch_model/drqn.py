@@ -59,7 +59,7 @@ class DeepRecurrentQNetwork(BaseModel):
         self.num_actions = env.get_action_space(handle)[0]
         self.batch_size, self.unroll_step, self.gamma, self.learning_rate = int(batch_size), int(unroll_step), reward_decay, learning_rate
         self.train_freq, self.target_update, self.eval_obs, self.use_double = train_freq, target_update, eval_obs, use_double
-        self.train_ct, self.agent_states = 0, {}
+        self.train_ct, self._agent_states = 0, {}
         if use_episode_train:
             raise NotImplementedError("use_episode_train (drqn.py:404, train_keep_hidden) is not provided")
         if device is None:
@@ -69,6 +69,16 @@ class DeepRecurrentQNetwork(BaseModel):
         self.target_net = _RecurrentQNet(self.view_space, self.feature_space, self.num_actions, use_dueling).to(self.device)
         self.target_net.load_state_dict(self.qnet.state_dict())
         self.optimizer = torch.optim.Adam(self.qnet.parameters(), lr=learning_rate)
+        # Acting on device-resident float32 observations goes through hand-written kernels (magent_amd/csrc/policy_drqn_f32.hip: the DQN's
+        # trunk, a GRU(512) cell, the head) with the GRU states in a device table keyed by agent id; MAGENT_POLICY_F32=torch keeps the
+        # PyTorch forward pass below, as for the DQN.  Numpy inputs, CPU devices and shapes the kernels do not take use that path too.
+        self._hip = None
+        if self.device.type == "cuda" and os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
+            try:
+                from .hip_policy import HipDrqnPolicyF32
+                self._hip = HipDrqnPolicyF32(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
+            except (ValueError, OSError, AttributeError):
+                self._hip = None
         # episodes: (views, features, actions, rewards, terminals) as device tensors; the oldest fall out (drqn.py:129-131)
         self.memory_size = memory_size
         self.replay_buffer = collections.deque(maxlen=memory_size)
@@ -79,6 +89,23 @@ class DeepRecurrentQNetwork(BaseModel):
         return torch.as_tensor(np.ascontiguousarray(x)).to(self.device, dtype)
 
     # ------------------------------------------------------------------ acting
+    @property
+    def agent_states(self):
+        """{agent id: GRU state [512]} after the last call; on the kernel path materialised from the device table when read"""
+        if self._agent_states is None:
+            return self._hip.states_dict()
+        return self._agent_states
+
+    @agent_states.setter
+    def agent_states(self, mapping):
+        """replaces the states of every agent ({} forgets them all)"""
+        self._agent_states = dict(mapping)
+
+    def _on_kernels(self, view, feature, n):
+        return (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
+                and feature.device == view.device and view.dtype == torch.float32 and feature.dtype == torch.float32 and view.is_contiguous()
+                and feature.is_contiguous() and tuple(view.shape) == (n,) + self.view_space and tuple(feature.shape) == (n,) + self.feature_space)
+
     @torch.no_grad()
     def infer_action(self, raw_obs, ids, policy="e_greedy", eps=0):
         """epsilon-greedy actions; the recurrent state of every agent is carried from its previous call by id"""
@@ -87,12 +114,20 @@ class DeepRecurrentQNetwork(BaseModel):
         if n == 0:
             self.agent_states = {}
             return np.empty(0, dtype=np.int32)
-        ids_host = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
-        zero = torch.zeros(_RecurrentQNet.STATE, device=self.device)
-        states = torch.stack([self.agent_states.get(int(i), zero) for i in ids_host]).unsqueeze(0)
-        q, states = self.qnet(self._tensor(view), self._tensor(feature), n, 1, states)
-        self.agent_states = {int(i): states[0, k] for k, i in enumerate(ids_host)}   # agents that are gone drop out
-        best = q.argmax(dim=1).to(torch.int32)
+        if self._on_kernels(view, feature, n):
+            if self._agent_states is not None:      # (states the dict path or a caller set: they become the device table)
+                self._hip.load_states(self._agent_states)
+                self._agent_states = None
+            ids_dev = ids.to(view.device, torch.int32) if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids, dtype=np.int32)).to(view.device)
+            best = self._hip.infer(view, feature, ids_dev)
+        else:
+            ids_host = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
+            zero = torch.zeros(_RecurrentQNet.STATE, device=self.device)
+            prev = self.agent_states
+            states = torch.stack([prev.get(int(i), zero) for i in ids_host]).unsqueeze(0)
+            q, states = self.qnet(self._tensor(view), self._tensor(feature), n, 1, states)
+            self.agent_states = {int(i): states[0, k] for k, i in enumerate(ids_host)}   # agents that are gone drop out
+            best = q.argmax(dim=1).to(torch.int32)
         if policy == "e_greedy":
             rnd = torch.randint(self.num_actions, best.shape, dtype=torch.int32, device=self.device)
             best = torch.where(torch.rand(best.shape, device=self.device) < eps, rnd, best)
@@ -126,6 +161,8 @@ class DeepRecurrentQNetwork(BaseModel):
 
     def train(self, sample_buffer, print_every=500):
         """add the round's episodes to the replay memory, then train on windows of `unroll_step` steps (zero initial state)"""
+        if self._hip is not None:
+            self._hip.dirty = True            # (the parameters change below; the kernels' packed copy is rebuilt at the next call)
         add_num = self._add_to_replay_buffer(sample_buffer)
         B, U = self.batch_size, self.unroll_step
         n_batches = int(self.train_freq * add_num / (B * U))
@@ -191,3 +228,5 @@ class DeepRecurrentQNetwork(BaseModel):
         self.target_net.load_state_dict(state["target"])
         self.optimizer.load_state_dict(state["optimizer"])
         self.train_ct = state.get("train_ct", 0)
+        if self._hip is not None:
+            self._hip.dirty = True

@@ -124,6 +124,25 @@ def fragment_order_f32(w):
     return w.reshape(n // 32, 32, k // 8, 2, 4).permute(2, 0, 3, 1, 4).contiguous().float().reshape(k // 8, n // 32, 64, 4)
 
 
+def _trunk_f32(q, shape, dev):
+    """conv1, conv2, dense_view, dense_emb of a _QNet / _RecurrentQNet (the same trunk) in f32 fragment order, with their biases"""
+    c = shape.view_c
+    w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
+    w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
+    w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
+    w2 = q.conv2.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 288)                      # K = tap * 32 + channel
+    wv = q.dense_view.weight.detach().float()                                                      # K = position * 32 + channel (NHWC flatten)
+    fk = (shape.feat + 7) // 8 * 8
+    we = _pad_k(q.dense_emb.weight.detach().float(), fk)
+    return {
+        "conv1": fragment_order_f32(w1.reshape(32, 72)), "conv2": fragment_order_f32(w2), "dense_view": fragment_order_f32(wv),
+        "dense_emb": fragment_order_f32(we),
+        "conv2_bias": q.conv2.bias.detach().float().contiguous(),
+        "dense_view_bias": q.dense_view.bias.detach().float().contiguous(),
+        "dense_emb_bias": q.dense_emb.bias.detach().float().contiguous(),
+    }
+
+
 class HipDqnPolicyF32(object):
     """greedy actions (and the Q values) of a dueling conv _QNet in float32 -- inputs, weights, activations, accumulation: the reference
     network's own arithmetic -- computed by k_dqn_conv_f32 + k_dqn_head_f32 on v_mfma_f32_32x32x2_f32 (magent_amd/csrc/policy_f32.hip)"""
@@ -142,24 +161,11 @@ class HipDqnPolicyF32(object):
     @torch.no_grad()
     def pack(self):
         q, dev = self.qnet, self.device
-        c = self.shape.view_c
-        w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
-        w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
-        w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
-        w2 = q.conv2.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 288)                      # K = tap * 32 + channel
-        wv = q.dense_view.weight.detach().float()                                                      # K = position * 32 + channel (NHWC flatten)
-        fk = (self.shape.feat + 7) // 8 * 8
-        we = _pad_k(q.dense_emb.weight.detach().float(), fk)
+        t = _trunk_f32(q, self.shape, dev)
         head = torch.zeros(32, 512, device=dev)
         head[:self.shape.n_action] = q.advantage.weight.detach().float()
         head[self.shape.n_action] = q.value.weight.detach().float()[0]
-        t = {
-            "conv1": fragment_order_f32(w1.reshape(32, 72)), "conv2": fragment_order_f32(w2), "dense_view": fragment_order_f32(wv),
-            "dense_emb": fragment_order_f32(we), "head": fragment_order_f32(head),
-            "conv2_bias": q.conv2.bias.detach().float().contiguous(),
-            "dense_view_bias": q.dense_view.bias.detach().float().contiguous(),
-            "dense_emb_bias": q.dense_emb.bias.detach().float().contiguous(),
-        }
+        t["head"] = fragment_order_f32(head)
         w = _Weights()
         for k, v in t.items():
             setattr(w, k, v.data_ptr())
@@ -188,4 +194,120 @@ class HipDqnPolicyF32(object):
                                                 self._work.data_ptr(), actions[beg:].data_ptr(), q[beg:].data_ptr() if want_q else None, stream)
             if rc != 0:
                 raise RuntimeError("policy_dqn_infer_f32 failed (%d)" % rc)
+        return (actions, q) if want_q else actions
+
+
+# ---------------------------------------------------------------------------------------------------- the recurrent network (drqn.py)
+class _DrqnWeights(ctypes.Structure):
+    _fields_ = [("trunk", _Weights), ("gru", ctypes.c_void_p), ("gru_bias", ctypes.c_void_p), ("gru_bias0", ctypes.c_void_p),
+                ("head", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("dueling", ctypes.c_int)]
+
+
+class HipDrqnPolicyF32(object):
+    """one acting step of a _RecurrentQNet in float32 -- the DQN's trunk (k_dqn_conv_f32 + k_dqn_head_f32), a GRU(512) cell (k_drqn_gru_f32),
+    the head and argmax (k_drqn_head_f32): magent_amd/csrc/policy_drqn_f32.hip -- and the GRU state of every agent id in device memory.
+
+    The state table is the last call's output: its ids in call order, their states (row k: the k-th id's), and for the next call's lookup
+    the ids sorted stably with their rows.  An id of the next call takes the state of its last occurrence in the table, any other id
+    starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  `lib`: a library other than the
+    product's (the tests' emulated build; its "device" memory is the host's, so the tensors are CPU tensors)."""
+    STATE = 512
+
+    def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072, lib=None):
+        self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
+        self.qnet, self.device, self.chunk = qnet, torch.device(device), int(chunk)
+        h, w, c = view_space
+        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        if qnet.rnn.hidden_size != self.STATE or not self._lib.policy_drqn_f32_supported(ctypes.byref(self.shape)):
+            raise ValueError("network shape not taken by the HIP f32 DRQN kernels")
+        self._packed, self._work = None, None
+        self.dirty = True
+        self.clear()
+
+    # ---- the state table
+    def clear(self):
+        z = torch.zeros(0, dtype=torch.int32, device=self.device)
+        self._ids, self._sorted, self._rows = z, z, z
+        self._states = torch.zeros((0, self.STATE), device=self.device)
+
+    def _set_table(self, ids, states):
+        self._ids, self._states = ids, states
+        self._sorted, perm = torch.sort(ids, stable=True)
+        self._rows = perm.to(torch.int32)
+
+    def states_dict(self):
+        """{id: state [512]} as the dict path keeps it (insertion in call order, a duplicated id's last row)"""
+        return {int(i): self._states[k] for k, i in enumerate(self._ids.tolist())}
+
+    def load_states(self, mapping):
+        """the table from a {id: state} mapping (an empty one empties it)"""
+        if len(mapping) == 0:
+            self.clear()
+            return
+        ids = torch.tensor([int(k) for k in mapping.keys()], dtype=torch.int32, device=self.device)
+        states = torch.stack([torch.as_tensor(v).to(self.device, torch.float32).reshape(self.STATE) for v in mapping.values()]).contiguous()
+        self._set_table(ids, states)
+
+    # ---- weights
+    @torch.no_grad()
+    def pack(self):
+        q, dev, S, A = self.qnet, self.device, self.STATE, self.shape.n_action
+        t = _trunk_f32(q, self.shape, dev)
+        rnn = q.rnn
+        wih, whh = rnn.weight_ih_l0.detach().float(), rnn.weight_hh_l0.detach().float()        # [3 S][S], gates r, z, n
+        bih, bhh = rnn.bias_ih_l0.detach().float(), rnn.bias_hh_l0.detach().float()
+        wcat = torch.cat([wih, whh], dim=1).reshape(3, S // 32, 32, 2 * S).permute(1, 0, 2, 3).reshape(3 * S, 2 * S)   # tile 3 T + gate
+        t["gru"] = fragment_order_f32(wcat)
+        bias = lambda bh: torch.stack([bih[:S] + bh[:S], bih[S:2 * S] + bh[S:2 * S], bih[2 * S:], bh[2 * S:]]).contiguous()
+        t["gru_bias"] = bias(bhh)
+        # a zero state: W_h 0 is 0, or NaN where a row of W_h is not finite (torch's W_h @ 0)
+        w0 = torch.where(torch.isfinite(whh).all(dim=1), torch.zeros_like(bhh), torch.full_like(bhh, float("nan")))
+        t["gru_bias0"] = bias(bhh + w0)
+        head, hb = torch.zeros(32, S, device=dev), torch.zeros(32, device=dev)
+        if q.use_dueling:
+            head[:A] = q.advantage.weight.detach().float()
+            head[A] = q.value.weight.detach().float()[0]
+            hb[A] = q.value.bias.detach().float()[0]
+        else:
+            head[:A] = q.value.weight.detach().float()
+            hb[:A] = q.value.bias.detach().float()
+        t["head"], t["head_bias"] = fragment_order_f32(head), hb
+        w = _DrqnWeights()
+        for k in ("conv1", "conv2", "dense_view", "dense_emb", "conv2_bias", "dense_view_bias", "dense_emb_bias"):
+            setattr(w.trunk, k, t[k].data_ptr())
+        for k in ("gru", "gru_bias", "gru_bias0", "head", "head_bias"):
+            setattr(w, k, t[k].data_ptr())
+        w.dueling = int(bool(q.use_dueling))
+        self._packed, self._w, self.dirty = t, w, False
+
+    # ---- one step
+    @torch.no_grad()
+    def infer(self, view, feature, ids, want_q=False):
+        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.
+        Enqueues the step on torch's current stream and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+        assert view.device == feature.device == ids.device and view.device.type == self.device.type
+        assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
+        assert view.shape[-1] == self.shape.view_c and ids.dtype == torch.int32 and view.shape[0] == feature.shape[0] == ids.shape[0]
+        if self.dirty:
+            self.pack()
+        n, dev = view.shape[0], view.device
+        ids = ids.clone(memory_format=torch.contiguous_format)        # (the table keeps it: the caller's buffer may be reused)
+        actions = torch.empty(n, dtype=torch.int32, device=dev)
+        q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=dev) if want_q else None
+        new_states = torch.empty((n, self.STATE), dtype=torch.float32, device=dev)
+        nbytes = ctypes.c_size_t(0)
+        self._lib.policy_drqn_f32_workspace_bytes(ctypes.byref(self.shape), min(n, self.chunk), ctypes.byref(nbytes))
+        if self._work is None or self._work.numel() < nbytes.value:
+            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        count = int(self._sorted.numel())
+        table = (self._sorted.data_ptr(), self._rows.data_ptr(), self._states.data_ptr()) if count else (None, None, None)
+        for beg in range(0, n, self.chunk):
+            m = min(self.chunk, n - beg)
+            rc = self._lib.policy_drqn_infer_f32(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
+                                                 ids[beg:].data_ptr(), table[0], table[1], table[2], count, new_states[beg:].data_ptr(),
+                                                 self._work.data_ptr(), actions[beg:].data_ptr(), q[beg:].data_ptr() if want_q else None, stream)
+            if rc != 0:
+                raise RuntimeError("policy_drqn_infer_f32 failed (%d)" % rc)
+        self._set_table(ids, new_states)
         return (actions, q) if want_q else actions

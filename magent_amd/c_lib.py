@@ -63,6 +63,9 @@ POLICY_ABI = [
     ("policy_dqn_f32_supported", [_vp]),
     ("policy_dqn_f32_act_bytes", [_vp, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_dqn_infer_f32", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("policy_drqn_f32_supported", [_vp]),
+    ("policy_drqn_f32_workspace_bytes", [_vp, _i, _c.POINTER(_c.c_size_t)]),
+    ("policy_drqn_infer_f32", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
 ]
 # include/magent_runtime_api.h PART 3, the rule-based actors: (name, restype, argtypes).  A table of its own, bound only where
 # the library exports it (the CPU checkers under oracle/ do not; `has_actor_api` says whether this one does).
@@ -72,6 +75,15 @@ ACTOR_ABI = [
     ("gather_infer_action", None, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     ("actor_infer_action_device", _c.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
+
+def declare_policy(lib):
+    """restype / argtypes of every POLICY_ABI symbol `lib` exports (also for the tests' emulated builds of the policy kernels)"""
+    for name, argtypes in POLICY_ABI:
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    return lib
+
 
 _cache = {}
 _lock = __import__("threading").Lock()
@@ -113,10 +125,7 @@ def _load(path=None):
             lib.has_device_api = False
             continue
         fn.restype, fn.argtypes = ctypes.c_int, argtypes
-    for name, argtypes in POLICY_ABI:
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    declare_policy(lib)
     lib.has_actor_api = True
     for name, restype, argtypes in ACTOR_ABI:
         fn = getattr(lib, name, None)

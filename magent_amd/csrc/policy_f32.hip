@@ -38,31 +38,17 @@
 #include <stdint.h>
 
 #include "../../include/magent_policy.h"
+#include "policy_f32_dev.h"
 #include "tune.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-__device__ __forceinline__ f32x16 mfma4(const f32x4 &w, const f32x4 &x, f32x16 acc) {     // the four k-steps of one group of 8 K-values
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[0], x[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[1], x[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[2], x[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[3], x[3], acc, 0, 0, 0);
-    return acc;
-}
-// relu that keeps a NaN a NaN, as torch.relu does (fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0, and a poisoned view or a diverged network would
-// then act on finite garbage).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, the cost of the v_max_f32 it replaces; -0 gives +0.
-__device__ __forceinline__ float relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
-__device__ __forceinline__ f32x4 relu4(const f32x16 &acc, int q) {
-    return f32x4{relu(acc[4 * q]), relu(acc[4 * q + 1]), relu(acc[4 * q + 2]), relu(acc[4 * q + 3])};
-}
-// torch.argmax's order of a Q row: a NaN above everything (the first NaN wins), then the larger value, the lower index among equals.  Does
-// (v, o) come before (best, arg)?
-__device__ __forceinline__ bool q_before(float v, int o, float best, int arg) {
-    return v != v ? (best == best || o < arg) : (best == best && (v > best || (v == best && o < arg)));
-}
+using magent_amd::f32::f32x16;
+using magent_amd::f32::f32x4;
+using magent_amd::f32::mfma4;
+using magent_amd::f32::q_before;
+using magent_amd::f32::relu;
+using magent_amd::f32::relu4;
 
 // conv2's output, dense_view's input: [group of 128 agents][K-chunk of 64 values = two positions][agent][64 values] (as policy.hip's
 // act_at, in floats): one k_dqn_head_f32 workgroup reads one contiguous 32 KB block per K-chunk
@@ -219,6 +205,7 @@ struct HeadArgs {
     int n, K, F, FK, n_action;
     int *actions;             // [n] argmax_a Q
     float *q;                 // [n][n_action] or null
+    float *x;                 // HIDDEN_OUT: [n][512] the hidden layer (the DRQN's GRU input); actions, q and wh are not used
 };
 
 // LDS images: rows of 16 float4 (activation chunk) / 64 float4 (hidden half), the unit index xor-ed with the row's low bits so that the 16
@@ -226,6 +213,8 @@ struct HeadArgs {
 __device__ __forceinline__ int act_slot(int row, int unit) { return row * 16 + (unit ^ (row & 15)); }
 __device__ __forceinline__ int hid_slot(int row, int unit) { return row * 64 + (unit ^ (row & 15)); }
 
+// HIDDEN_OUT (the DRQN's trunk, policy_f32_dev.h: dqn_f32_trunk): the hidden layer goes to A.x instead of through the dueling head
+template <bool HIDDEN_OUT>
 __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     f32x4 *s_act = (f32x4 *)s_raw;                         // [2][128 agents][16 units], swizzled -- and, behind the main loop,
@@ -298,14 +287,18 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
         ((float *)s_feat)[row * A.FK + f] = (f < A.F && a0 + row < A.n) ? A.feat[(size_t)(a0 + row) * A.F + f] : 0.0f;
     }
     // relu(acc + bias) -> one half of the hidden layer: lane (agent, g) of output tile w holds units 32 w + 8 q + 4 g + 0..3
-    auto hidden_out = [&](const float *bias) {
+    auto hidden_out = [&](const float *bias, int half) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
-                s_hid[hid_slot(32 * j + r32, 8 * w + 2 * q + g)] = v;
+                if constexpr (HIDDEN_OUT) {
+                    if (a0 + 32 * j + r32 < A.n) *(f32x4 *)(A.x + (size_t)(a0 + 32 * j + r32) * 512 + 256 * half + 32 * w + 8 * q + 4 * g) = v;
+                } else {
+                    s_hid[hid_slot(32 * j + r32, 8 * w + 2 * q + g)] = v;
+                }
             }
         }
     };
@@ -322,9 +315,9 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
             }
         }
     };
-    hidden_out(A.bv);          // (the main loop's last barrier is behind us: nobody reads the activation buffers any more)
+    hidden_out(A.bv, 0);       // (the main loop's last barrier is behind us: nobody reads the activation buffers any more)
     __syncthreads();
-    head_half(0);
+    if constexpr (!HIDDEN_OUT) head_half(0);
     // the feature embedding: K = FK, all eight waves (output tile w, four agent tiles)
 #pragma unroll
     for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
@@ -336,8 +329,12 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
             acc[j] = mfma4(we, x, acc[j]);
         }
     }
+    if constexpr (HIDDEN_OUT) {
+        hidden_out(A.be, 1);
+        return;
+    }
     __syncthreads();           // the first half of the head has read relu(dense_view)
-    hidden_out(A.be);
+    hidden_out(A.be, 1);
     __syncthreads();
     head_half(1);
     if (w < 4) {
@@ -387,6 +384,10 @@ static size_t conv_lds(const PolicyDqnShape *s, int ta) {
 }
 static int conv_ta(const PolicyDqnShape *s) { return conv_lds(s, 4) <= 160 * 1024 ? 4 : 2; }
 
+// the two kernels: conv, then the head -- the dueling head and the argmax (x == null), or only the hidden layer into x (the DRQN's trunk)
+static int launch_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, const float *view, const float *feat, int n, void *act_workspace,
+                      int *actions, float *q, float *x, void *stream);
+
 }  // namespace
 
 extern "C" {
@@ -401,6 +402,20 @@ int policy_dqn_f32_act_bytes(const PolicyDqnShape *s, int n, size_t *bytes) {
 }
 int policy_dqn_infer_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, const float *view, const float *feat, int n, void *act_workspace,
                          int *actions, float *q, void *stream) {
+    return launch_f32(s, w, view, feat, n, act_workspace, actions, q, nullptr, stream);
+}
+
+}  // extern "C"
+
+int magent_amd::f32::dqn_f32_trunk(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, const float *view, const float *feat, int n,
+                                   void *act_workspace, float *x, void *stream) {
+    return x ? launch_f32(s, w, view, feat, n, act_workspace, nullptr, nullptr, x, stream) : 1;
+}
+
+namespace {
+
+static int launch_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, const float *view, const float *feat, int n, void *act_workspace,
+                      int *actions, float *q, float *x, void *stream) {
     if (!policy_dqn_f32_supported(s)) return 1;
     if (n <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
@@ -418,7 +433,8 @@ int policy_dqn_infer_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, 
     if (!lds_ok_dev[dev]) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_conv_f32<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 2;
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_conv_f32<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head_f32<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
         lds_ok_dev[dev] = true;
     }
     ConvArgs C{};
@@ -432,9 +448,10 @@ int policy_dqn_infer_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, 
     HeadArgs Hd{};
     Hd.act = (const float *)act_workspace; Hd.feat = feat; Hd.wv = (const f32x4 *)w->dense_view; Hd.we = (const f32x4 *)w->dense_emb; Hd.wh = (const f32x4 *)w->head;
     Hd.bv = w->dense_view_bias; Hd.be = w->dense_emb_bias; Hd.value_bias = w->value_bias;
-    Hd.n = n; Hd.K = H2 * W2 * 32; Hd.F = s->feat; Hd.FK = (s->feat + 7) / 8 * 8; Hd.n_action = s->n_action; Hd.actions = actions; Hd.q = q;
-    hipLaunchKernelGGL(k_dqn_head_f32, dim3((n + HEAD_M - 1) / HEAD_M), dim3(HEAD_THREADS), HEAD_LDS, st, Hd);
+    Hd.n = n; Hd.K = H2 * W2 * 32; Hd.F = s->feat; Hd.FK = (s->feat + 7) / 8 * 8; Hd.n_action = s->n_action; Hd.actions = actions; Hd.q = q; Hd.x = x;
+    if (x) hipLaunchKernelGGL(k_dqn_head_f32<true>, dim3((n + HEAD_M - 1) / HEAD_M), dim3(HEAD_THREADS), HEAD_LDS, st, Hd);
+    else hipLaunchKernelGGL(k_dqn_head_f32<false>, dim3((n + HEAD_M - 1) / HEAD_M), dim3(HEAD_THREADS), HEAD_LDS, st, Hd);
     return hipGetLastError() == hipSuccess ? 0 : 3;
 }
 
-}  // extern "C"
+}  // namespace
