@@ -322,10 +322,18 @@ class Scenario(object):
     game     : built-in game name, or ("custom-name", args...) for one of the CUSTOM configs
     events   : {step: [("add", group, method, kw) | ("walls", method, kw) | ("reset", placements)]} applied before
                that step's observations -- mid-episode placement and a second episode on the same engine (the RNG
-               stream continues across reset, GridWorld.cc:72-118)"""
+               stream continues across reset, GridWorld.cc:72-118)
+    observed : (run_cycle / run_cycle_batch only) the groups that are given view / feature buffers: None (all), a list, or a callable
+               step -> list.  A group left out is not observed by the checker's leg either and has no view%d / feat%d key
+    rewarded : likewise for the reward buffers (reward%d)
+    probe    : steps BEFORE whose cycle both legs observe EVERY non-empty group through the ordinary calls (probe_view%d, probe_feat%d:
+               the last_reward / last_action columns and the hp cells of a group that was left out), and read every group's reward
+               behind the cycle (probe_reward%d); when any is given, the same is done once more behind the last cycle"""
 
     def __init__(self, name, game, map_size, seed=12345, place=(), steps=10, action_seed=0, walls=0,
-                 acting=None, over=None, clear_every=1, obs_every=1, events=None, settings=None, engine=True, still=()):
+                 acting=None, over=None, clear_every=1, obs_every=1, events=None, settings=None, engine=True, still=(),
+                 observed=None, rewarded=None, probe=()):
+        self.observed, self.rewarded, self.probe = observed, rewarded, tuple(probe)
         self.name, self.game, self.map_size, self.seed = name, game, map_size, seed
         self.engine = engine                # False: the engine refuses this game (turn_mode); the oracle is pinned on it all the same
         self.settings = settings or {}      # extra GridWorld settings (food_mode, ...) and, for custom games, type overrides
@@ -341,6 +349,32 @@ class Scenario(object):
             n_move = env.get_view2attack(h)[0] - (2 if self.settings.get("turn_mode") else 0)
             a[:] = n_move // 2              # (the move tables are circle ranges: the centre, (0, 0), is the middle entry)
         return a
+
+    def groups_at(self, which, step, n_group):
+        """the groups that `which` (self.observed or self.rewarded) names at `step`"""
+        sel = which(step) if callable(which) else which
+        return list(range(n_group)) if sel is None else list(sel)
+
+    def probe_before(self, env, handles, step, rec):
+        """a probe step: every non-empty group observed through the reference ABI, whatever `observed` says"""
+        if step not in self.probe:
+            return
+        for g, h in enumerate(handles):
+            if env.get_num(h) > 0:
+                v, f = env.get_observation(h)
+                rec["probe_view%d" % g], rec["probe_feat%d" % g] = v.copy(), f.copy()
+
+    def probe_after(self, env, handles, step, rec):
+        """behind a probe step's cycle every group's reward is read through the reference ABI (behind clear_dead: what Agent::init_reward and
+        Group::init_reward left); behind the last cycle every non-empty group is observed once more"""
+        if step in self.probe:
+            for g, h in enumerate(handles):
+                rec["probe_reward%d" % g] = np.array(env.get_reward(h), dtype=np.float32)
+        if self.probe and step == self.steps - 1:
+            for g, h in enumerate(handles):
+                if env.get_num(h) > 0:
+                    v, f = env.get_observation(h)
+                    rec["end_view%d" % g], rec["end_feat%d" % g] = v.copy(), f.copy()
 
     def config(self):
         if callable(self.game):
@@ -480,12 +514,13 @@ def mean_info_trace(sc, lib, steps=6):
     return out
 
 
-def run_cycle(sc, lib, fused, preset=False):
+def run_cycle(sc, lib, fused, preset=False, reduce=None):
     """Play `sc` one environment CYCLE at a time (observe + set_action per group, step, rewards, clear_dead) and record what a
     caller of magent_amd.EnvBatch.cycle can see: observations, ids, rewards, done, and the state AFTER clear_dead.
 
     fused=True : the HIP engine through env_cycle_many (EnvBatch.cycle: two launches per cycle for small worlds), device buffers
-    fused=False: any library, the same calls one after the other through the reference API (the CPU checkers take this leg)"""
+    fused=False: any library, the same calls one after the other through the reference API (the CPU checkers take this leg)
+    reduce     : what is kept of a step's record (hash_rec for worlds whose trajectories do not fit in memory)"""
     assert sc.clear_every == 1
     env, handles = sc.build(lib)
     rs = np.random.RandomState(sc.action_seed)
@@ -501,21 +536,24 @@ def run_cycle(sc, lib, fused, preset=False):
         sc.apply_events(env, step)
         nums = [env.get_num(h) for h in handles]
         acts = [sc.draw(rs, env, g, h, nums[g]) if g in acting else None for g, h in enumerate(handles)]
-        observe = [step % sc.obs_every == 0 and nums[g] > 0 for g in range(len(handles))]
+        seen, paid = sc.groups_at(sc.observed, step, len(handles)), sc.groups_at(sc.rewarded, step, len(handles))
+        observe = [step % sc.obs_every == 0 and nums[g] > 0 and g in seen for g in range(len(handles))]
+        sc.probe_before(env, handles, step, rec)
         for g, h in enumerate(handles):
             rec["id%d" % g] = env.get_agent_id(h)
         if fused:
             views = [torch.empty((nums[g],) + env.get_view_space(h), device=dev) if observe[g] else None for g, h in enumerate(handles)]
             feats = [torch.empty((nums[g],) + env.get_feature_space(h), device=dev) if observe[g] else None for g, h in enumerate(handles)]
             d_acts = [torch.from_numpy(a).to(dev) if a is not None else None for a in acts]
-            rews = [torch.empty(nums[g], device=dev) for g in range(len(handles))]
+            rews = [torch.empty(nums[g], device=dev) if g in paid else None for g in range(len(handles))]
             device_sync(lib)
             done = batch.cycle([views], [feats], [d_acts], [rews])[0]
             env.sync()
             for g in range(len(handles)):
                 if observe[g]:
                     rec["view%d" % g], rec["feat%d" % g] = views[g].cpu().numpy(), feats[g].cpu().numpy()
-                rec["reward%d" % g] = rews[g].cpu().numpy()
+                if g in paid:
+                    rec["reward%d" % g] = rews[g].cpu().numpy()
         else:
             assert not (preset and fused)
             for g, h in enumerate(handles):       # (preset: every set_action ahead of every observation)
@@ -529,7 +567,8 @@ def run_cycle(sc, lib, fused, preset=False):
                     env.set_action(h, acts[g])
             done = env.step()
             for g, h in enumerate(handles):
-                rec["reward%d" % g] = env.get_reward(h)
+                if g in paid:
+                    rec["reward%d" % g] = env.get_reward(h)
             env.clear_dead()
         rec["done"] = np.array([done], dtype=np.int32)
         for g, h in enumerate(handles):       # the state after clear_dead
@@ -537,20 +576,23 @@ def run_cycle(sc, lib, fused, preset=False):
             rec["pos%d" % g] = env.get_pos(h)
             rec["alive%d" % g] = env.get_alive(h).astype(np.uint8)
             rec["ids_after%d" % g] = env.get_agent_id(h)
-        out.append(rec)
+        sc.probe_after(env, handles, step, rec)
+        out.append(reduce(rec) if reduce else rec)
         if all(env.get_num(h) == 0 for h in handles) and not any(k > step for k in sc.events):
             break
     return out
 
 
-def run_cycle_batch(scs, lib, preset=False, envs_out=None):
+def run_cycle_batch(scs, lib, preset=False, envs_out=None, counters_out=None, reduce=None):
     """run_cycle(fused=True) for SEVERAL environments of one configuration at once: a single magent_amd.EnvBatch, so that for
     small worlds all of them share one pair of launches per cycle (k_render_batch + k_step_solo_batch).  Returns one trajectory
     per scenario; an environment whose groups are all empty keeps cycling with the others (its trajectory stops there, as
     run_cycle's does).
     preset: the actions are handed over by env_set_action_device BEFORE the call and the cycle is given none (the NULL entries
     include/magent_runtime_api.h documents): the observations then show the new last_action, as the reference's do when
-    set_action comes first (GridWorld.cc:386-396) -- the checker's leg is run_cycle(..., preset=True)."""
+    set_action comes first (GridWorld.cc:386-396) -- the checker's leg is run_cycle(..., preset=True).
+    counters_out: a list that receives, per cycle, every environment's count of cycles through the batched pipeline so far
+    (pipeline_stats()[6]) -- which environment was in the pipeline in which cycle (expected_pipe_cycles)."""
     import torch
     built = [sc.build(lib) for sc in scs]
     envs, handles = [b[0] for b in built], [b[1] for b in built]
@@ -570,13 +612,16 @@ def run_cycle_batch(scs, lib, preset=False, envs_out=None):
             sc.apply_events(env, step)
             nums = [env.get_num(h) for h in hs]
             acts = [rss[k].randint(env.get_action_space(h)[0], size=nums[g]).astype(np.int32) if g in acting else None for g, h in enumerate(hs)]
-            observe = [step % sc.obs_every == 0 and nums[g] > 0 for g in range(len(hs))]
+            seen, paid = sc.groups_at(sc.observed, step, len(hs)), sc.groups_at(sc.rewarded, step, len(hs))
+            observe = [step % sc.obs_every == 0 and nums[g] > 0 and g in seen for g in range(len(hs))]
+            if live[k] and step < sc.steps:
+                sc.probe_before(env, hs, step, rec)
             for g, h in enumerate(hs):
                 rec["id%d" % g] = env.get_agent_id(h)
             views.append([torch.empty((nums[g],) + env.get_view_space(h), device=dev) if observe[g] else None for g, h in enumerate(hs)])
             feats.append([torch.empty((nums[g],) + env.get_feature_space(h), device=dev) if observe[g] else None for g, h in enumerate(hs)])
             d_acts.append([torch.from_numpy(a).to(dev) if a is not None else None for a in acts])
-            rews.append([torch.empty(nums[g], device=dev) for g in range(len(hs))])
+            rews.append([torch.empty(nums[g], device=dev) if g in paid else None for g in range(len(hs))])
             recs.append(rec); observes.append(observe)
         device_sync(lib)
         if preset:
@@ -587,13 +632,16 @@ def run_cycle_batch(scs, lib, preset=False, envs_out=None):
             dones = batch.cycle(views, feats, None, rews)
         else:
             dones = batch.cycle(views, feats, d_acts, rews)
+        if counters_out is not None:
+            counters_out.append([env.pipeline_stats()[6] for env in envs])
         for k, (sc, env, hs) in enumerate(zip(scs, envs, handles)):
             env.sync()
             rec = recs[k]
             for g in range(len(hs)):
                 if observes[k][g]:
                     rec["view%d" % g], rec["feat%d" % g] = views[k][g].cpu().numpy(), feats[k][g].cpu().numpy()
-                rec["reward%d" % g] = rews[k][g].cpu().numpy()
+                if rews[k][g] is not None:
+                    rec["reward%d" % g] = rews[k][g].cpu().numpy()
             rec["done"] = np.array([dones[k]], dtype=np.int32)
             for g, h in enumerate(hs):
                 rec["num%d" % g] = np.array([env.get_num(h)], dtype=np.int32)
@@ -601,10 +649,123 @@ def run_cycle_batch(scs, lib, preset=False, envs_out=None):
                 rec["alive%d" % g] = env.get_alive(h).astype(np.uint8)
                 rec["ids_after%d" % g] = env.get_agent_id(h)
             if live[k] and step < sc.steps:
-                out[k].append(rec)
+                sc.probe_after(env, hs, step, rec)
+                out[k].append(reduce(rec) if reduce else rec)
                 if all(env.get_num(h) == 0 for h in hs) and not any(e > step for e in sc.events):
                     live[k] = False
     return out
+
+
+def expected_pipe_cycles(scs, trajs, tune=""):
+    """per cycle, which environments of ONE EnvBatch the engine sends through the batched pipeline (Env::cycle_many / Env::pipe_eligible restated
+    for the plain games of pipe_partial_scenarios; `trajs`: the checker's trajectories, whose id%d arrays give the sizes at the start of every
+    cycle): a plain world of which no two observed, non-empty groups look through different windows under minimap_mode; from `batch_pipe_min`
+    (1537) agents on -- at every size when MAGENT_TUNE sets batch_pipe_min=1 or fixes attack_pairs (the one-launch step is off then); and only
+    when at least two environments of the call qualify.  Returns the running counts, [cycle][environment], as run_cycle_batch's counters_out."""
+    forced = "batch_pipe_min=1" in tune or "attack_pairs=" in tune
+    windows = []
+    for sc in scs:
+        cfg = sc.config()
+        ranges = [cfg.agent_type_dict[cfg.groups[g]]["view_range"] for g in range(len(cfg.groups))]
+        windows.append((bool(cfg.config_dict.get("minimap_mode")), [(r.radius, r.angle) for r in ranges]))
+    counts, out = [0] * len(scs), []
+    for step in range(max(sc.steps for sc in scs)):
+        ok = []
+        for sc, traj, (minimap, win) in zip(scs, trajs, windows):
+            assert step < len(traj), "expected_pipe_cycles: every environment of the batch plays every cycle"
+            nums = [len(traj[step]["id%d" % g]) for g in range(len(win))]
+            seen = [g for g in sc.groups_at(sc.observed, step, len(win)) if nums[g] > 0 and step % sc.obs_every == 0]
+            ok.append(sum(nums) > 0 and (forced or sum(nums) >= 1537) and not (minimap and len(set(win[g] for g in seen)) > 1))
+        for k in range(len(scs)):
+            counts[k] += ok[k] and sum(ok) >= 2
+        out.append(list(counts))
+    return out
+
+
+def check_pipe_partial(lib, what):
+    """pipe_partial_scenarios in ONE EnvBatch on engine library `lib`, every environment against the oracle driven alone through the reference
+    call sequence; which environment went through the batched pipeline in which cycle, from the engine's own counter, against
+    expected_pipe_cycles under this process's MAGENT_TUNE.  Returns the final counts."""
+    tune = os.environ.get("MAGENT_TUNE", "")
+    scs = pipe_partial_scenarios()
+    want = [run_cycle(sc, ensure_oracle(), fused=False) for sc in scs]
+    for sc, w in zip(scs, want):
+        if sc.name.startswith("gather_bench"):   # food is eaten and the group that nobody looks at compacted in (far more than) half of the steps
+            sizes = [len(w[0]["id0"])] + [int(r["num0"][0]) for r in w]
+            assert len(w) == sc.steps >= 12 and sum(b < a for a, b in zip(sizes, sizes[1:])) * 2 >= sc.steps, (sc.name, sizes)
+        assert not sc.probe or (any(k.startswith("probe_view") for k in w[sc.probe[0]]) and any(k.startswith("end_view") for k in w[-1])), sc.name
+    expect = expected_pipe_cycles(scs, want, tune)
+    # (the restatement itself, pinned: with the defaults the eight partial worlds play every cycle in the pipeline but for the two that
+    # gather_changing goes alone; pipe_a falls below 1537 agents in its last two; the two-launch world never gets there)
+    forced = "batch_pipe_min=1" in tune or "attack_pairs=" in tune
+    assert expect[-1] == [12, 12, 12, 12, 12, 12, 10, 12, 12 if forced else 10, 12 if forced else 0], expect[-1]
+    assert [c[6] for c in expect[3:7]] == [4, 4, 4, 5], expect      # (the counter stands still in cycles 4 and 5)
+    seen, counters = [], []
+    got = run_cycle_batch(scs, lib, envs_out=seen, counters_out=counters)
+    for sc, w, g in zip(scs, want, got):
+        assert_same(w, g, "%s (%s)" % (sc.name, what))
+    assert counters == expect, (what, counters, expect)
+    return counters[-1]
+
+
+def check_cycle_partial(lib, what):
+    """cycle_partial_scenarios through run_cycle(fused=True) one by one and as batches of three (the two-launch cycle: k_render_batch +
+    k_step_solo_batch), every environment against the oracle driven alone through the reference call sequence"""
+    scs = cycle_partial_scenarios()
+    want = [run_cycle(sc, ensure_oracle(), fused=False) for sc in scs]
+    for sc, w in zip(scs, want):
+        assert_same(w, run_cycle(sc, lib, fused=True), "%s (alone, %s)" % (sc.name, what))
+    for pick in ([0, 1, 2], [3, 2, 1]):
+        for k, g in zip(pick, run_cycle_batch([scs[k] for k in pick], lib)):
+            assert_same(want[k], g, "%s (batch of three, %s)" % (scs[k].name, what))
+
+
+def hash_rec(rec):
+    """a step's record reduced to {key: xxh3-128 hex digest} as run_hashed does (the same digests as tests/golden/digests_fullsize.json)"""
+    import xxhash
+    return {k: xxhash.xxh3_128(np.ascontiguousarray(v).reshape(-1).view(np.uint8)).hexdigest() for k, v in rec.items()}
+
+
+def fullsize_partial_batch():
+    """bench.py's `extra.gather_500_100k` line at its size, in ONE EnvBatch with a battle world: (A) fullsize_scenarios()["c4_gather500"]
+    itself -- gather 500 x 500, 20,000 food + 100,000 agents, its seed and action seed -- with the food never observed, never acting and
+    without a reward buffer; (B) the same with other seeds; (C) the first 8 steps of "c2_battle200" (2 x 2000, everybody observed).  With
+    groups left out run_cycle makes the reference's calls in run's order but for the left-out ones, so the arrays of A and C that mean the
+    same in both drivers (FULLSIZE_PARTIAL_KEYS) equal the compiled reference's committed digests of those scenarios."""
+    import copy
+    full = fullsize_scenarios()
+    a, c = copy.deepcopy(full["c4_gather500"]), copy.deepcopy(full["c2_battle200"])
+    a.observed, a.rewarded, a.probe, c.steps = [1], [1], (4,), 8
+    b = copy.deepcopy(a)
+    b.name, b.seed, b.action_seed = "c4_gather500_other_seeds", 777, 9
+    assert a.steps == b.steps == c.steps == 8 and a.acting == [1]
+    return [a, b, c]
+
+
+# (num / pos / alive are recorded before clear_dead by run and behind it by run_cycle: those are compared with the oracle only)
+FULLSIZE_PARTIAL_KEYS = {"c4_gather500": ["done", "feat1", "id0", "id1", "reward1", "view1"],
+                         "c2_battle200": ["done", "feat0", "feat1", "id0", "id1", "reward0", "reward1", "view0", "view1"]}
+
+
+def check_fullsize_partial(lib, want, gold):
+    """fullsize_partial_batch on engine library `lib`, hashed step by step: every key of all three worlds against `want` (the oracle driven
+    alone: [run_cycle(sc, oracle, fused=False, reduce=hash_rec)]), FULLSIZE_PARTIAL_KEYS of A and C against `gold` (the compiled reference's
+    digests); all three worlds in the batched pipeline in every cycle.  Returns the engines' render kernels (engine_stats()[6])."""
+    scs = fullsize_partial_batch()
+    seen, counters = [], []
+    got = run_cycle_batch(scs, lib, envs_out=seen, counters_out=counters, reduce=hash_rec)
+    for sc, w, g in zip(scs, want, got):
+        assert_same_hashed(w, g, sc.name + " vs the oracle driven alone")
+        if sc.name in FULLSIZE_PARTIAL_KEYS:
+            assert len(g) == 8
+            for s, rec in enumerate(g):
+                for k in FULLSIZE_PARTIAL_KEYS[sc.name]:
+                    assert k in rec, "%s step %d: %s was not recorded" % (sc.name, s, k)
+                    assert rec[k] == gold[sc.name][s][k], "%s step %d: %s differs from the compiled reference's digest" % (sc.name, s, k)
+                if sc.name == "c4_gather500":
+                    assert not any(k in rec for k in ("view0", "feat0", "reward0")), (s, sorted(rec))
+    assert counters == [[s + 1] * 3 for s in range(8)], counters
+    return [e.engine_stats()[6] for e in seen]
 
 
 def run_hashed(sc, lib, device_io=False, env_out=None):
@@ -717,7 +878,9 @@ def preset_batch_scenarios():
 def pipe_batch_scenarios():
     """environments of one env_cycle_many call that take all three of its forms: plain worlds beyond the one-launch step (the batched pipeline,
     pipe.hip: deaths from the first step, a group that dies out, reinforcements that change every grid size mid-episode, a non-square
-    large_map_mode world), a world small enough for the two-launch cycle, and gather (its two groups look through different windows: it goes alone)"""
+    large_map_mode world), a world small enough for the two-launch cycle, and gather with BOTH groups observed (under minimap_mode its two groups
+    look through different windows, 3 x 3 and 15 x 15: one minimap per environment and cycle does not do, Env::pipe_eligible and Env::cycle_eligible
+    refuse it and it goes alone.  With only the agents observed -- as bench.py drives it -- gather goes through the pipeline: pipe_partial_scenarios)"""
     rnd = lambda g, n: (g, "random", {"n": n})
     S = scenarios()
     return [Scenario("pipe_a", "battle", 60, place=[rnd(0, 1000), rnd(1, 1000)], steps=12, action_seed=91, over={"small": {"hp": 4, "damage": 3}}),
@@ -725,6 +888,72 @@ def pipe_batch_scenarios():
                      events={4: [("add", 1, "random", {"n": 900})], 8: [("add", 0, "fill", {"pos": (2, 2), "size": (30, 20)})]}),
             Scenario("pipe_c", "battle", 104, place=[rnd(0, 2600), rnd(1, 60)], steps=12, action_seed=93, over={"small": {"damage": 11}}),
             S["battle_brawl"], S["gather"]]
+
+
+def gather_schedule(step):
+    """the observed groups of the `*_changing` gather worlds: the agents (a 15 x 15 window) for four cycles; food (3 x 3) AND agents for two --
+    different windows under minimap_mode: one minimap per environment and cycle does not do, the world leaves the batch and goes alone; the
+    agents again (back in; the minimap folded into the cycles that went alone was theirs); then the food alone -- the other window, whatever
+    minimap the cycle before prepared for "the same groups" is stale"""
+    return [1] if step < 4 else [0, 1] if step < 6 else [1] if step < 9 else [0]
+
+
+def late_schedule(step):
+    """the observed groups of the `*_late` battle worlds: nobody before step 3 (no window is known until then: nothing to fold the next
+    minimap for), everybody every third step from there on"""
+    return [0, 1] if step >= 3 and step % 3 == 0 else []
+
+
+def pipe_partial_scenarios():
+    """worlds of one env_cycle_many call in which groups are left out, as bench.py's gather line leaves the food out (never observed, never
+    acting, no reward buffer) -- all of them plain worlds from 1537 agents on for the whole episode: the batched pipeline (pipe.hip), asserted
+    cycle by cycle from the engine's own counter (expected_pipe_cycles):
+      gather_bench_a/_b : gather as the bench drives it, two replicas with different seeds; food at hp 5 (one hit of the agents' damage 6
+                          kills): food is eaten and the unobserved, unrewarded group compacted from the first steps on
+      battle_*          : hp 4 / damage 3 (kills in every step); a side that is observed and rewarded but does not act; one that acts but is
+                          not observed; one that is neither observed, nor acting, nor rewarded; one side rewarded but not observed while the
+                          other is observed but not rewarded
+      gather_changing   : gather_schedule; battle_late: late_schedule
+      pipe_a, battle_brawl (12 steps of it): a fully observed pipeline world and a two-launch world in the same call
+    Every scenario probes in the middle and at the end (Scenario.probe)."""
+    import copy
+    rnd = lambda g, n: (g, "random", {"n": n})
+    hot = {"small": {"hp": 4, "damage": 3}}
+    brawl = copy.deepcopy(scenarios()["battle_brawl"])
+    brawl.steps = 12
+    return [Scenario("gather_bench_a", "gather", 70, place=[rnd(0, 500), rnd(1, 2400)], steps=12, seed=501, action_seed=101, over={"food": {"hp": 5}},
+                     acting=[1], observed=[1], rewarded=[1], probe=(6,)),
+            Scenario("gather_bench_b", "gather", 70, place=[rnd(0, 600), rnd(1, 2500)], steps=12, seed=502, action_seed=102, over={"food": {"hp": 5}},
+                     acting=[1], observed=[1], rewarded=[1], probe=(5,)),
+            Scenario("battle_seen_idle", "battle", 64, place=[rnd(0, 1100), rnd(1, 1100)], steps=12, seed=503, action_seed=103, over=hot,
+                     acting=[1], probe=(6,)),
+            Scenario("battle_blind_actor", "battle", 64, place=[rnd(0, 1100), rnd(1, 1100)], steps=12, seed=504, action_seed=104, over=hot,
+                     observed=[1], probe=(6,)),
+            Scenario("battle_neither", "battle", 64, place=[rnd(0, 1100), rnd(1, 1100)], steps=12, seed=505, action_seed=105, over=hot,
+                     acting=[0], observed=[0], rewarded=[0], probe=(7,)),
+            Scenario("battle_paid_blind", "battle", 64, place=[rnd(0, 1100), rnd(1, 1100)], steps=12, seed=506, action_seed=106, over=hot,
+                     observed=[0], rewarded=[1], probe=(6,)),
+            Scenario("gather_changing", "gather", 70, place=[rnd(0, 500), rnd(1, 2400)], steps=12, seed=507, action_seed=107, over={"food": {"hp": 5}},
+                     acting=[1], observed=gather_schedule, rewarded=[1], probe=(7,)),
+            Scenario("battle_late", "battle", 64, place=[rnd(0, 1100), rnd(1, 1100)], steps=12, seed=508, action_seed=108, over=hot,
+                     observed=late_schedule, rewarded=lambda step: [step % 2], probe=(5,)),
+            pipe_batch_scenarios()[0], brawl]
+
+
+def cycle_partial_scenarios():
+    """the same shapes below 1537 agents: the two-launch cycle (k_render_batch + k_step_solo_batch; Env::cycle_prepare makes the next
+    cycle's minimap for "the same groups") -- scenarios()["gather"] (300 food + 1200 agents) with only the agents observed and rewarded, the
+    same with gather_schedule, a battle world with one side left out altogether, one observed late"""
+    rnd = lambda g, n: (g, "random", {"n": n})
+    hot = {"small": {"hp": 4, "damage": 3}}
+    return [Scenario("gather_partial", "gather", 60, place=[rnd(0, 300), rnd(1, 1200)], acting=[1], steps=20, action_seed=11, over={"food": {"hp": 5}},
+                     observed=[1], rewarded=[1], probe=(9,)),
+            Scenario("gather_partial_changing", "gather", 60, place=[rnd(0, 300), rnd(1, 1200)], acting=[1], steps=14, action_seed=12, seed=77,
+                     over={"food": {"hp": 5}}, observed=gather_schedule, rewarded=[1], probe=(7,)),
+            Scenario("battle_partial", "battle", 30, place=[rnd(0, 200), rnd(1, 200)], steps=16, action_seed=13, seed=78, over=hot,
+                     acting=[1], observed=[1], rewarded=[1], probe=(8,)),
+            Scenario("battle_partial_late", "battle", 30, place=[rnd(0, 200), rnd(1, 200)], steps=16, action_seed=14, seed=79, over=hot,
+                     acting=[0, 1], observed=late_schedule, rewarded=[0], probe=(8,))]
 
 
 def episode_scenarios():
@@ -1032,9 +1261,21 @@ def fuzz_scenario(seed):
         goal_mode = bool(rg.rand() < 0.5)
         for _ in range(int(rg.randint(1, 4))):
             events.setdefault(int(rg.randint(0, 8)), []).append(("goal", int(rg.randint(G))))
-    return Scenario("fuzz%d" % seed, make, 0, seed=int(rs.randint(1, 1 << 20)), place=place, steps=int(rs.randint(6, 14)),
-                    action_seed=seed, walls=int(area * float(rs.choice([0, 0, 0.02, 0.08]))), acting=acting,
-                    clear_every=int(rs.choice([1, 1, 1, 2])), obs_every=int(rs.choice([1, 1, 2])), events=events)
+    sc = Scenario("fuzz%d" % seed, make, 0, seed=int(rs.randint(1, 1 << 20)), place=place, steps=int(rs.randint(6, 14)),
+                  action_seed=seed, walls=int(area * float(rs.choice([0, 0, 0.02, 0.08]))), acting=acting,
+                  clear_every=int(rs.choice([1, 1, 1, 2])), obs_every=int(rs.choice([1, 1, 2])), events=events)
+    # FUZZ_PARTIAL=1 (with FUZZ_PLAIN=1; drawn behind everything else: the game of a seed stays what it is without it): groups left out of
+    # the observations (at least one stays) and, independently, of the rewards -- run_cycle / run_cycle_batch hand over NULL entries for
+    # them -- and, where there is no minimap (one minimap per environment and cycle: Env::pipe_eligible), a window of its own per group;
+    # everybody is observed in the middle and at the end (Scenario.probe)
+    if fuzz_plain and os.environ.get("FUZZ_PARTIAL", "0") == "1":
+        sc.observed = [g for g in range(G) if rs.rand() < 0.6] or [int(rs.randint(G))]
+        sc.rewarded = [g for g in range(G) if rs.rand() < 0.6]
+        if not minimap:
+            for t in specs:
+                t["view_range"] = float(rs.choice([1, 2, 3, 4, 5, 6, 7]))
+        sc.probe = (sc.steps // 2,)
+    return sc
 
 
 def digest(trajectory):

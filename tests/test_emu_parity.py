@@ -191,6 +191,54 @@ def test_emulated_batched_pipeline(emu):
         assert p.returncode == 0 and "ok" in p.stdout, (extra, p.stdout[-1500:] + p.stderr[-3000:])
 
 
+PARTIAL_LEGS = {
+    "default": {},
+    "scrambled": {"HIPEMU_SCRAMBLE": "7"},
+    # every observed group of 65536 window cells or more renders by launches of its own inside Env::pipe_prepare (the battle sides' 1100 x 13 x 13,
+    # the gather agents' 2400 x 15 x 15; the food's 3 x 3 windows stay with the batch) / none does
+    "own_renders": {"MAGENT_TUNE": "pipe_own=1"},
+    "no_own_renders": {"MAGENT_TUNE": "pipe_own=4096", "HIPEMU_SCRAMBLE": "2"},
+    "generic_batch_render": {"MAGENT_TUNE": "pipe_sweep=0"},
+    "sweeping_batch_render": {"MAGENT_TUNE": "pipe_sweep=3", "HIPEMU_SCRAMBLE": "9"},
+    # every step of every environment runs out and is finished by the host: Env::pipe_after with NULL reward entries
+    "host_finishes": {"MAGENT_TUNE": "attack_pairs=0"},
+    "host_finishes_own_renders": {"MAGENT_TUNE": "attack_pairs=0,pipe_own=1", "HIPEMU_SCRAMBLE": "4"},
+    "one_pair_every_world": {"MAGENT_TUNE": "attack_pairs=1,batch_pipe_min=1"},
+    "minimap_not_folded": {"MAGENT_TUNE": "fold_minimap=0"},
+}
+
+
+@pytest.mark.parametrize("leg", sorted(PARTIAL_LEGS))
+def test_emulated_batched_pipeline_with_groups_left_out(emu, leg):
+    """what bench.py's gather line does and no other test did: env_cycle_many over worlds in which a populated group has NULL view / feat /
+    action / reward entries (helpers.pipe_partial_scenarios: gather with the food left out, every combination on battle worlds, observed sets
+    that change during the episode, beside a fully observed world and a two-launch world), every environment against the oracle driven ALONE
+    through the reference call sequence -- which observes and rewards the same groups only, and observes everybody at a step in the middle and
+    at the end (a left-out group's last_reward / last_action columns, its hp in the others' view cells).  The engine's own counter says
+    cycle by cycle which environment was in the pipeline (helpers.expected_pipe_cycles: compared exactly).  Then the same shapes below 1537
+    agents on the two-launch cycle (helpers.cycle_partial_scenarios), alone and as batches of three."""
+    code = ("import os, sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import helpers as H\n"
+            "emu = H.ensure_emu()\n"
+            "last = H.check_pipe_partial(emu, 'batched pipeline, groups left out, hipemu')\n"
+            "H.check_cycle_partial(emu, 'two-launch cycle, groups left out, hipemu')\n"
+            "print('ok', last)\n") % (ROOT, os.path.join(ROOT, "tests"))
+    p = subprocess.run([sys.executable, "-c", code], env=H.merge_env(os.environ, {"OMP_NUM_THREADS": "1"}, PARTIAL_LEGS[leg]), capture_output=True, text=True, timeout=1500)
+    assert p.returncode == 0 and "ok" in p.stdout, (leg, p.stdout[-1500:] + p.stderr[-3000:])
+
+
+def test_emulated_fuzz_batched_pipeline_with_groups_left_out(emu):
+    """a slice of tests/test_gpu_fullsize.py::test_fuzz_batched_pipeline's FUZZ_PARTIAL leg on the emulator: random plain games with a random
+    subset of the groups observed, another one rewarded, a window of its own per group where there is no minimap -- three environments per
+    game in one EnvBatch, every world through the batched pipeline (batch_pipe_min=1), each against the oracle driven alone; the second leg
+    with every step finished by the host.  The run's own count says that every game had environments in the pipeline."""
+    for tune, n in (("batch_pipe_min=1", 40), ("batch_pipe_min=1,attack_pairs=0", 16)):
+        env = H.merge_env(os.environ, {"OMP_NUM_THREADS": "1", "FUZZ_BATCH": "3", "FUZZ_PLAIN": "1", "FUZZ_PARTIAL": "1", "MAGENT_TUNE": tune})
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_parity.py"), "oracle", "emu", "0", str(n)], env=env,
+                             capture_output=True, text=True, timeout=1500)
+        assert out.returncode == 0 and "%d seeds, 0 failures" % n in out.stdout and "batched pipeline (pipe.hip): %d " % n in out.stdout, (tune, out.stdout[-3000:], out.stderr[-2000:])
+
+
 @pytest.mark.parametrize("env,needle", [({"MAGENT_SOLO_STEP": "0"}, "MAGENT_TUNE=solo_step="), ({"MAGENT_RENDER_PAD": "1"}, "has no successor"),
                                         ({"MAGENT_TUNE": "solo_stepp=0"}, "unknown entry")],
                          ids=["removed_variable_with_successor", "removed_variable_without", "unknown_tune_key"])

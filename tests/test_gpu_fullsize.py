@@ -224,12 +224,14 @@ def test_fuzz_batched_pipeline():
     """three environments per random PLAIN game (FUZZ_PLAIN=1: one-cell bodies, subject-paying attack / kill rules, one view window -- what
     the pipeline of plain games takes) in ONE magent_amd.EnvBatch with every world sent through the batched pipeline (batch_pipe_min=1:
     pipe.hip's one launch per phase for all of them), each against the oracle driven alone through the reference call sequence; the second
-    leg with one optimistic pair of death-rank rounds (steps that run out are finished by the host, environment by environment)"""
-    for tune in ("batch_pipe_min=1", "batch_pipe_min=1,attack_pairs=1"):
-        env = dict(os.environ, OMP_NUM_THREADS="1", FUZZ_BATCH="3", FUZZ_PLAIN="1", MAGENT_TUNE=tune)
+    leg with one optimistic pair of death-rank rounds (steps that run out are finished by the host, environment by environment); the third
+    with groups left out (FUZZ_PARTIAL=1: a random subset of the groups observed, another one rewarded -- NULL entries for the others --, a
+    window of its own per group where there is no minimap; everybody observed through the ordinary calls in the middle and at the end)"""
+    for tune, extra in (("batch_pipe_min=1", {}), ("batch_pipe_min=1,attack_pairs=1", {}), ("batch_pipe_min=1", {"FUZZ_PARTIAL": "1"})):
+        env = dict(os.environ, OMP_NUM_THREADS="1", FUZZ_BATCH="3", FUZZ_PLAIN="1", MAGENT_TUNE=tune, **extra)
         out = subprocess.run([sys.executable, os.path.join(H.ROOT, "tools", "fuzz_parity.py"), "oracle", "hip", "0", "150"], env=env,
                              capture_output=True, text=True, timeout=1500)
-        assert out.returncode == 0 and "150 seeds, 0 failures" in out.stdout and "batched pipeline (pipe.hip): 150" in out.stdout, (tune, out.stdout[-3000:], out.stderr[-2000:])
+        assert out.returncode == 0 and "150 seeds, 0 failures" in out.stdout and "batched pipeline (pipe.hip): 150" in out.stdout, (tune, extra, out.stdout[-3000:], out.stderr[-2000:])
 
 
 @pytest.mark.parametrize("tune", ["pipe_sweep=0", "pipe_sweep=3", "pipe_sweep=32"])
@@ -248,6 +250,32 @@ def test_batched_pipeline_render_forms(tune):
             "print('ok')\n") % (H.ROOT, os.path.join(H.ROOT, "tests"))
     p = subprocess.run([sys.executable, "-c", code], env=H.merge_env(os.environ, {"OMP_NUM_THREADS": "1"}, {"MAGENT_TUNE": tune}), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "ok" in p.stdout, (tune, p.stdout[-1500:] + p.stderr[-3000:])
+
+
+def test_fullsize_mixed_batch_with_the_food_left_out(tmp_path):
+    """bench.py's `extra.gather_500_100k.eight_replicas_one_gpu` call shape at its size under a checker: ONE EnvBatch of two gather 500 x 500
+    worlds (20,000 food + 100,000 agents; the food has NULL view / feat / action / reward entries) and a
+    battle 200 x 200 world, 8 steps, hashed step by step.  Replica A is `c4_gather500` itself and the battle world `c2_battle200`: their
+    observations, ids, rewards and done flags against the digests of the COMPILED REFERENCE (helpers.FULLSIZE_PARTIAL_KEYS: an absent array
+    fails); all three against the oracle driven alone, every key, everybody observed through the ordinary calls before step 4 and at the
+    end.  Once with the defaults (100,000 x 15 x 15 cells: each gather world renders by launches of its own) and once with pipe_own raised
+    so that the batch's launch renders them; every world in the pipeline in every cycle (the engine's counter, exactly)."""
+    scs = H.fullsize_partial_batch()
+    want = [H.run_cycle(sc, H.ensure_oracle(), fused=False, reduce=H.hash_rec) for sc in scs]
+    for sc, w in zip(scs, want):          # (the oracle's own trajectory of A and C is the reference's, before any GPU time is spent)
+        for k in H.FULLSIZE_PARTIAL_KEYS.get(sc.name, ()):
+            assert [r[k] for r in w] == [r[k] for r in GOLD[sc.name][:8]], (sc.name, k)
+    with open(str(tmp_path / "want.json"), "w") as f:
+        json.dump(want, f)
+    code = ("import json, sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import torch, helpers as H\n"
+            "want = json.load(open(sys.argv[1]))\n"
+            "gold = json.load(open(H.os.path.join(H.GOLDEN_DIR, 'digests_fullsize.json')))\n"
+            "print('ok', H.check_fullsize_partial(H.HIP_LIB, want, gold))\n") % (H.ROOT, os.path.join(H.ROOT, "tests"))
+    for tune in (None, "pipe_own=512"):      # (512 x 65536 cells: beyond the 22.5 M of a gather world's agents)
+        p = subprocess.run([sys.executable, "-c", code, str(tmp_path / "want.json")], env=H.merge_env(os.environ, {"OMP_NUM_THREADS": "1"}, {"MAGENT_TUNE": tune} if tune else {}),
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0 and "ok" in p.stdout, (tune, p.stdout[-1500:] + p.stderr[-3000:])
 
 
 def test_fuzz_batched_cycle():

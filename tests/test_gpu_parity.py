@@ -93,6 +93,33 @@ def test_batched_pipeline(oracle):
     assert all(e.pipeline_stats()[6] >= 6 for e in seen), [e.pipeline_stats() for e in seen]
 
 
+def test_batched_pipeline_with_groups_left_out(oracle):
+    """env_cycle_many as bench.py's gather line drives it: a populated group with NULL view / feat / action / reward entries (the food of two
+    gather worlds, eaten and compacted every step; every combination on battle worlds; observed sets that change during the episode; beside a
+    fully observed pipeline world and a two-launch world in the same call), every environment against the oracle driven alone through the
+    reference call sequence with the same groups left out, everybody observed in the middle and at the end; which environment was in the
+    pipeline in which cycle is compared exactly with the engine's own counter.  Then the same shapes below 1537 agents (two-launch cycle)."""
+    last = H.check_pipe_partial(H.HIP_LIB, "batched pipeline, groups left out")
+    assert last == [12, 12, 12, 12, 12, 12, 10, 12, 10, 0], last
+    H.check_cycle_partial(H.HIP_LIB, "two-launch cycle, groups left out")
+
+
+@pytest.mark.parametrize("tune", ["pipe_own=1", "pipe_sweep=0", "pipe_sweep=3", "attack_pairs=0", "attack_pairs=1,batch_pipe_min=1", "fold_minimap=0"])
+def test_batched_pipeline_with_groups_left_out_variants(tune):
+    """the same with every observed group of 65536 window cells or more rendering by its own launches inside Env::pipe_prepare, with the batch's
+    render as generic / as few sweeping workgroups, with every step finished by the host (Env::pipe_after with NULL reward entries), with
+    one optimistic pair and every world in the pipeline, without the folded minimap (the engine reads MAGENT_TUNE once: a process each)"""
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import torch, helpers as H\n"
+            "last = H.check_pipe_partial(H.HIP_LIB, 'batched pipeline, groups left out')\n"
+            "H.check_cycle_partial(H.HIP_LIB, 'two-launch cycle, groups left out')\n"
+            "print('ok', last)\n") % (H.ROOT, os.path.join(H.ROOT, "tests"))
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, "-c", code], env=H.merge_env(os.environ, {"OMP_NUM_THREADS": "1"}, {"MAGENT_TUNE": tune}), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "ok" in p.stdout, (tune, p.stdout[-1500:] + p.stderr[-3000:])
+
+
 def test_batched_pipeline_over_a_long_episode(oracle):
     """the batched pipeline over what only acts with the length of an episode (the claim words' epoch window, refilled every 63 steps by every
     environment of the batch for itself; the carried round stamps; the batch's budget of optimistic rounds: three, four while some environment's is raised):

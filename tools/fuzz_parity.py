@@ -5,6 +5,10 @@
   FUZZ_BATCH=3 python tools/fuzz_parity.py oracle hip 0 300   # three environments per game in one EnvBatch (one launch pair for all)
   FUZZ_CYCLE=1 python tools/fuzz_parity.py oracle hip 0 300   # the HIP leg through env_cycle_many (two launches per cycle), the
                                                               # other leg through the reference call sequence
+  FUZZ_PLAIN=1 FUZZ_PARTIAL=1 FUZZ_BATCH=3 MAGENT_TUNE=batch_pipe_min=1 python tools/fuzz_parity.py oracle hip 0 150
+                                                              # plain games with groups left out of the observations / rewards (NULL
+                                                              # entries), three environments per game through the batched pipeline
+  FUZZ_PLAIN=1 FUZZ_PARTIAL=1 FUZZ_CYCLE=1 python tools/fuzz_parity.py ref oracle 0 300   # ... the generator itself: reference == oracle
 """
 import os
 import sys
