@@ -120,6 +120,41 @@ int policy_drqn_infer_f32(const PolicyDqnShape *shape, const PolicyDrqnWeightsF3
                           const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
                           void *workspace, int *actions, float *q, void *stream);
 
+/* ---- one acting step of the advantage actor-critic (magent_amd/builtin/torch_model/a2c.py: _ActorCritic.forward, then the action draw)
+ * in float32 -- magent_amd/csrc/policy_a2c_f32.hip.  No convolution: the flattened view (K = view_h * view_w * view_c values, in the
+ * order env_get_observation_device writes them) feeds a dense layer.  Weights in f32 fragment order, biases in natural order:
+ *   dense_view : K padded to a multiple of 8 with zero weights                                                        [KP/8][8][64][4]
+ *   dense_emb  : feature index (padded to a multiple of 8)                                                            [FK/8][8][64][4]
+ *   dense      : K = dense_view's 256 units, then dense_emb's 256                                                     [64][16][64][4]
+ *   comm[s]    : CommNet step s = 0, 1 (use_comm): C_s and H_s [512][512] side by side, K = the 512 means of the OTHER agents' units,
+ *                then the agent's own 512; NULL without use_comm                                                      [128][16][64][4]
+ *   head       : K = the 512 hidden units; outputs 0..n_action-1 = policy logits, output n_action = value, the rest zero  [64][64][4]
+ * dense_view_bias, dense_emb_bias float[256]; dense_bias float[512]; head_bias float[32] per output of `head`. */
+typedef struct {
+    const void *dense_view, *dense_emb, *dense;
+    const void *comm[2];
+    const void *head;
+    const float *dense_view_bias, *dense_emb_bias, *dense_bias, *head_bias;
+    int use_comm;
+} PolicyA2cWeightsF32;
+
+/* 1 if the A2C kernels take this shape: view_h, view_w, view_c >= 1 with view_h * view_w * view_c <= 4096 (view_c is NOT limited to 7:
+ * there is no convolution; the bound keeps the packed dense_view inside one 4 MB L2), 1 <= feat <= 64, 1 <= n_action <= 31 (the policy's
+ * outputs and the value share one 32-wide tile) */
+int policy_a2c_f32_supported(const PolicyDqnShape *shape);
+/* size of the workspace of one call with n agents: two (use_comm: three) float[n][512] layers, and with use_comm the column sums'
+ * partial blocks */
+int policy_a2c_f32_workspace_bytes(const PolicyDqnShape *shape, int n, int use_comm, size_t *bytes);
+/* One step of n agents.  u float[n]: one uniform number in [0, 1) per agent.  policy (optional) float[n][n_action] = clamp(softmax(logits),
+ * 1e-10, 1 - 1e-10); value (optional) float[n].  The draw, in float32 and in this order: c_0 = p_0, c_a = c_(a-1) + p_a,
+ * t = u * c_(n_action-1); actions[i] = the smallest a with c_a > t, or n_action - 1 if there is none (rounding, a NaN in the row): always
+ * inside [0, n_action).  With use_comm the means run over ALL n agents of the call; the column sums are taken over blocks of 256 agents
+ * in agent order and then over the blocks in order (no atomics), so the result is a function of the inputs alone.  The workspace is
+ * 16-byte aligned.  Enqueues its kernels (3, with use_comm 9) on `stream` and returns 0, or non-zero with nothing written if the shape is
+ * not supported / a pointer is missing / the workspace is misaligned / a launch failed. */
+int policy_a2c_infer_f32(const PolicyDqnShape *shape, const PolicyA2cWeightsF32 *weights, const float *view, const float *feature, int n,
+                         const float *u, void *workspace, int *actions, float *policy, float *value, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

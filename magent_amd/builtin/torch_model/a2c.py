@@ -65,6 +65,23 @@ class AdvantageActorCritic(BaseModel):
         self.device = torch.device(device)
         self.net = _ActorCritic(self.view_space, self.feature_space, self.num_actions, use_comm).to(self.device)
         self.optimizer = torch.optim.Adam(self.net.parameters(), lr=learning_rate)
+        # Acting on device-resident float32 observations goes through hand-written kernels (magent_amd/csrc/policy_a2c_f32.hip: the network,
+        # CommNet included, the softmax and an inverse-CDF draw from torch.rand); MAGENT_POLICY_F32=torch keeps the PyTorch forward pass and
+        # torch.multinomial below, as for the DQN.  Numpy inputs, CPU devices and shapes the kernels do not take use that path too.
+        self._hip = None
+        if self.device.type == "cuda" and os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
+            try:
+                from .hip_policy import HipA2cPolicyF32
+                self._hip = HipA2cPolicyF32(self.net, self.view_space, self.feature_space, self.num_actions, self.device)
+            except (ValueError, OSError, AttributeError):
+                self._hip = None
+
+    def _on_kernels(self, view, feature):
+        n = len(view)
+        return (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
+                and self.device.index in (None, view.device.index)
+                and feature.device == view.device and view.dtype == torch.float32 and feature.dtype == torch.float32 and view.is_contiguous()
+                and feature.is_contiguous() and tuple(view.shape) == (n,) + self.view_space and tuple(feature.shape) == (n,) + self.feature_space)
 
     def _tensor(self, x, dtype=torch.float32):
         if isinstance(x, torch.Tensor):
@@ -77,12 +94,16 @@ class AdvantageActorCritic(BaseModel):
         view, feature = raw_obs[0], raw_obs[1]
         if len(view) == 0:
             return np.empty(0, dtype=np.int32)
+        if self._on_kernels(view, feature):
+            return self._hip.infer(view, feature)
         policy, _ = self.net(self._tensor(view), self._tensor(feature))
         acts = torch.multinomial(policy, 1).squeeze(1).to(torch.int32)
         return acts if isinstance(view, torch.Tensor) else acts.cpu().numpy()
 
     def train(self, sample_buffer, print_every=1000):
         """one gradient step over all samples of the round; returns ([pg_loss, vf_loss, ent_loss], mean state value)"""
+        if self._hip is not None:
+            self._hip.dirty = True            # (the parameters change below; the kernels' packed copy is rebuilt at the next call)
         views, features, actions, returns = [], [], [], []
         for ep in sample_buffer.episodes():
             m = len(ep.rewards)
@@ -132,3 +153,5 @@ class AdvantageActorCritic(BaseModel):
         self.net.load_state_dict(state["net"])
         self.optimizer.load_state_dict(state["optimizer"])
         self.train_ct = state.get("train_ct", 0)
+        if self._hip is not None:
+            self._hip.dirty = True

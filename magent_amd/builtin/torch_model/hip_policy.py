@@ -311,3 +311,92 @@ class HipDrqnPolicyF32(object):
                 raise RuntimeError("policy_drqn_infer_f32 failed (%d)" % rc)
         self._set_table(ids, new_states)
         return (actions, q) if want_q else actions
+
+
+# ---------------------------------------------------------------------------------------------------- the actor-critic (a2c.py)
+class _A2cWeights(ctypes.Structure):
+    _fields_ = [("dense_view", ctypes.c_void_p), ("dense_emb", ctypes.c_void_p), ("dense", ctypes.c_void_p), ("comm", ctypes.c_void_p * 2),
+                ("head", ctypes.c_void_p), ("dense_view_bias", ctypes.c_void_p), ("dense_emb_bias", ctypes.c_void_p),
+                ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
+
+
+class HipA2cPolicyF32(object):
+    """one acting step of an _ActorCritic in float32 -- the two input layers (k_a2c_trunk_f32), dense 512 and the two CommNet steps
+    (k_a2c_layer_f32, the column sums by k_a2c_colsum_part_f32 + k_a2c_colsum_f32), the policy and value heads, the softmax and the draw
+    (k_a2c_head_f32): magent_amd/csrc/policy_a2c_f32.hip.
+
+    The draw is the inverse CDF of one uniform number per agent (include/magent_policy.h: policy_a2c_infer_f32).  Without CommNet a call
+    of n agents goes to the kernels `chunk` agents at a time (every agent's row is its own).  With CommNet the mean of the other agents
+    spans the call, so the whole n goes to ONE C call whatever `chunk` is: the column sums are then taken over the same blocks of agents
+    in the same order, and the result does not depend on `chunk`.  `lib`: a library other than the product's (the tests' emulated build;
+    its "device" memory is the host's, so the tensors are CPU tensors)."""
+
+    def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
+        self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
+        self.net, self.device, self.chunk = net, torch.device(device), int(chunk)
+        h, w, c = view_space
+        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        self.use_comm = net.comm is not None
+        if net.dense.in_features != 512 or net.dense.out_features != 512 or not self._lib.policy_a2c_f32_supported(ctypes.byref(self.shape)):
+            raise ValueError("network shape not taken by the HIP f32 A2C kernels")
+        self._packed, self._work = None, None
+        self.dirty = True
+
+    @torch.no_grad()
+    def pack(self):
+        net, dev, A = self.net, self.device, self.shape.n_action
+        wv = net.dense_view.weight.detach().float()
+        t = {
+            "dense_view": fragment_order_f32(_pad_k(wv, (wv.shape[1] + 7) // 8 * 8)),
+            "dense_emb": fragment_order_f32(_pad_k(net.dense_emb.weight.detach().float(), (self.shape.feat + 7) // 8 * 8)),
+            "dense": fragment_order_f32(net.dense.weight.detach().float()),
+            "dense_view_bias": net.dense_view.bias.detach().float().contiguous(),
+            "dense_emb_bias": net.dense_emb.bias.detach().float().contiguous(),
+            "dense_bias": net.dense.bias.detach().float().contiguous(),
+        }
+        head, hb = torch.zeros(32, 512, device=dev), torch.zeros(32, device=dev)
+        head[:A], hb[:A] = net.policy.weight.detach().float(), net.policy.bias.detach().float()
+        head[A], hb[A] = net.value.weight.detach().float()[0], net.value.bias.detach().float()[0]
+        t["head"], t["head_bias"] = fragment_order_f32(head), hb
+        w = _A2cWeights()
+        for k, v in t.items():
+            setattr(w, k, v.data_ptr())
+        if self.use_comm:
+            for s, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
+                t["comm%d" % s] = fragment_order_f32(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
+                w.comm[s] = t["comm%d" % s].data_ptr()
+        w.use_comm = int(self.use_comm)
+        self._packed, self._w, self.dirty = t, w, False       # (the tensors stay alive as long as the pointers are in use)
+
+    @torch.no_grad()
+    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
+        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
+        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
+        probabilities [n][A] and / or the values [n] if asked for"""
+        assert view.device == feature.device and view.device.type == self.device.type
+        assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
+        assert tuple(view.shape[1:]) == (self.shape.view_h, self.shape.view_w, self.shape.view_c) and view.shape[0] == feature.shape[0]
+        if self.dirty:
+            self.pack()
+        n, dev, A = view.shape[0], view.device, self.shape.n_action
+        if u is None:
+            u = torch.rand(n, device=dev)
+        assert u.device == dev and u.dtype == torch.float32 and u.is_contiguous() and u.shape == (n,)
+        actions = torch.empty(n, dtype=torch.int32, device=dev)
+        policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
+        value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
+        chunk = n if self.use_comm else self.chunk
+        nbytes = ctypes.c_size_t(0)
+        self._lib.policy_a2c_f32_workspace_bytes(ctypes.byref(self.shape), min(n, chunk), int(self.use_comm), ctypes.byref(nbytes))
+        if self._work is None or self._work.numel() < nbytes.value:
+            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        for beg in range(0, n, max(chunk, 1)):
+            m = min(chunk, n - beg)
+            rc = self._lib.policy_a2c_infer_f32(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
+                                                u[beg:].data_ptr(), self._work.data_ptr(), actions[beg:].data_ptr(),
+                                                policy[beg:].data_ptr() if want_policy else None, value[beg:].data_ptr() if want_value else None, stream)
+            if rc != 0:
+                raise RuntimeError("policy_a2c_infer_f32 failed (%d)" % rc)
+        out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
+        return out if len(out) > 1 else actions

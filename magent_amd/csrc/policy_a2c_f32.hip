@@ -1,0 +1,417 @@
+// policy_a2c_f32.hip -- one acting step of the advantage actor-critic (magent_amd/builtin/torch_model/a2c.py: _ActorCritic.forward, then
+// the action draw), inference only, in float32 on v_mfma_f32_32x32x2_f32.
+//
+//   network:  xv = relu(flat(view) Wv^T + bv) [256] || xe = relu(feature We^T + be) [256]  ->  h = relu([xv | xe] Wd^T + bd) [512]
+//             CommNet (use_comm), twice:  h <- tanh(others C_s^T + h H_s^T + skip),  skip = the h above,
+//                                         others_i = (sum_j h_j - h_i) / (n - 1) over ALL n agents of the call (zeros for n == 1)
+//             logits = h Wp^T + bp [A],  value = h Wval^T + bval;   p = clamp(softmax(logits), 1e-10, 1 - 1e-10)
+//             draw:  c_0 = p_0, c_a = c_(a-1) + p_a, t = u c_(A-1);  action = the smallest a with c_a > t, else A - 1
+//
+// Operands and fragments as in policy_f32.hip: A = weights (lane l: output l & 31), B = activations (lane l: agent l & 31), a lane group g
+// reads values 4 g .. 4 g + 3 of a group of 8 K-values as one float4 that feeds four MFMAs; a result lane (agent, g) holds outputs
+// 8 q + 4 g + 0..3 of its 32-wide tile, natural order.  Every result column (agent) of an MFMA depends on that agent's operands alone, so
+// an agent's row does not depend on where in a tile, a workgroup or a launch it sits.
+//
+// k_a2c_trunk_f32 : the two input layers as k_dqn_head_f32 does its dense layer -- 128 agents per workgroup of 8 waves, wave w owns output
+//   tile w for all four agent tiles (one weight float4 from L2 and four activation float4 from LDS feed 16 MFMAs).  The view rows are K =
+//   H W C floats, 4-byte aligned only (battle: 1183), so a K-chunk of 64 values per agent goes through registers into LDS by 4-byte
+//   loads -- a wave reads 64 consecutive floats of one row -- double buffered; values past K are zeros (K is padded to a multiple of 8 with
+//   zero weights), rows past n repeat row n - 1 and are not stored.  x = [xv | xe] goes to HBM as float[n][512].
+// k_a2c_layer_f32 : a [n] x [512] layer over K = 512 (<false>: h = relu(x Wd^T + bd)) or K = 1024 (<true>: one CommNet step as ONE GEMM,
+//   [others | h] against [C_s | H_s] side by side; others is formed from the h row and the column sums as the operand is fed, tanh in
+//   registers).  A wave owns 32 agents x 4 output tiles (four accumulators: per group of 8 K-values one activation float4 and four weight
+//   float4 feed 16 MFMAs), operands of the next two groups load while the current two's 32 MFMAs run; as k_drqn_gru_f32, from L2 / HBM.
+// k_a2c_colsum_part_f32 + k_a2c_colsum_f32 : the CommNet column sums without float atomics -- partial sums over blocks of 256 agents (block
+//   b: agents 256 b .. 256 b + 255 of the call, added in agent order), then the blocks added in block order.  The sums are a function of
+//   the call's inputs alone.
+// k_a2c_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 (outputs 0..A-1 the policy's, output A the value's), softmax with the
+//   row maximum subtracted, clamp, and the draw by the lane that holds the agent's action 0 (the row goes through LDS: a lane pair holds it).
+//
+// NaN contract: relu is IEEE maximum, tanhf and expf keep a NaN, the clamp is two comparisons (a NaN fails both and stays);
+// the row maximum ignores a NaN (fmaxf) but the NaN reaches the row's sum through its own exp, so the whole row is NaN as F.softmax's.  A
+// row with a NaN draws action A - 1 (no c_a > t holds).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "../../include/magent_policy.h"
+#include "policy_f32_dev.h"
+
+namespace {
+
+using magent_amd::f32::f32x16;
+using magent_amd::f32::f32x4;
+using magent_amd::f32::mfma4;
+using magent_amd::f32::relu;
+
+constexpr int HID = 512;
+// ---------------------------------------------------------------------------------------------------- the input layers
+constexpr int TR_THREADS = 512, TR_M = 128, TR_KC = 64;            // 128 agents per workgroup of 8 waves; K staged 64 values at a time
+constexpr int TR_ABUF = TR_M * (TR_KC / 4);                          // float4 units of one activation buffer: 32 KB
+constexpr int TR_FMAX = 64;                                          // most features (padded to 8)
+constexpr int TR_KMAX = 4096;                                        // most view values: the packed dense_view (K x 256 floats) stays inside one 4 MB L2
+constexpr size_t TR_LDS = ((size_t)2 * TR_ABUF + (size_t)TR_M * (TR_FMAX / 4)) * 16;      // two activation buffers + the features: 96 KB
+
+struct TrunkArgs {
+    const float *view;        // [n][K]
+    const float *feat;        // [n][F]
+    const f32x4 *wv;          // dense_view, f32 fragment order [KG][8 tiles][64]     (KG = K rounded up to 8, in groups)
+    const f32x4 *we;          // dense_emb,  [FK / 8][8 tiles][64]                     (FK = F rounded up to 8)
+    const float *bv, *be;     // [256] biases, natural order
+    int n, K, KG, F, FK;
+    float *x;                 // [n][512] relu(dense_view) || relu(dense_emb)
+};
+
+// rows of 16 float4, the unit index xor-ed with the row's low bits (policy_f32.hip: act_slot)
+__device__ __forceinline__ int act_slot(int row, int unit) { return row * 16 + (unit ^ (row & 15)); }
+
+__global__ void __launch_bounds__(TR_THREADS) k_a2c_trunk_f32(TrunkArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
+    f32x4 *s_act = (f32x4 *)s_raw;                         // [2][128 agents][16 units], swizzled
+    float *s_feat = (float *)(s_act + 2 * TR_ABUF);        // [128 agents][FK]
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
+    const int a0 = blockIdx.x * TR_M;
+    const int n_groups = A.KG, total = (n_groups + 7) / 8;
+    const f32x4 *wbase = A.wv + (size_t)w * 64 + l;        // fragment (group m, tile w) = wbase[m * 8 * 64]
+
+    for (int k = tid; k < TR_M * A.FK; k += TR_THREADS) {
+        const int row = k / A.FK, f = k - row * A.FK;
+        s_feat[k] = (f < A.F && a0 + row < A.n) ? A.feat[(size_t)(a0 + row) * A.F + f] : 0.0f;
+    }
+    // staging: wave w moves value l of the chunk for rows w, w + 8, .. w + 120 (64 consecutive floats of a row per load)
+    float ar[16];
+    auto aload = [&](int c) {
+        const int k = c * TR_KC + l;
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const float *row = A.view + (size_t)min(a0 + w + 8 * i, A.n - 1) * A.K;
+            ar[i] = k < A.K ? row[k] : 0.0f;
+        }
+    };
+    auto astore = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) ((float *)(s_act + buf * TR_ABUF + act_slot(w + 8 * i, l >> 2)))[l & 3] = ar[i];
+    };
+    f32x4 wr[2][8];          // the wave's weight fragments: this chunk's and the next one's
+    auto wload = [&](int c, f32x4 (&dst)[8]) {
+#pragma unroll
+        for (int m = 0; m < 8; m++) dst[m] = wbase[(size_t)min(c * 8 + m, n_groups - 1) * 8 * 64];
+    };
+    f32x16 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
+
+    aload(0);
+    wload(0, wr[0]);
+    astore(0);
+    if (total > 1) aload(1);
+    __syncthreads();
+    auto chunk = [&](int c, f32x4 (&wc)[8], f32x4 (&wn)[8]) __attribute__((always_inline)) {
+        const int buf = c & 1;
+        const int groups = min(8, n_groups - c * 8);
+        if (c + 1 < total) wload(c + 1, wn);
+        f32x4 x[2][4];
+        auto xread = [&](int m, f32x4 (&dst)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) dst[j] = s_act[buf * TR_ABUF + act_slot(32 * j + r32, 2 * m + g)];
+        };
+        xread(0, x[0]);
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            if (m < 7) xread(m + 1, x[(m + 1) & 1]);
+            if (m < groups) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = mfma4(wc[m], x[m & 1][j], acc[j]);
+            }
+            if (m == 1 && c + 1 < total) astore(buf ^ 1);    // the next chunk (its buffer was last read two barriers back)
+        }
+        if (c + 2 < total) aload(c + 2);
+        __syncthreads();
+    };
+    for (int c = 0; c < total; c += 2) {
+        chunk(c, wr[0], wr[1]);
+        if (c + 1 < total) chunk(c + 1, wr[1], wr[0]);
+    }
+    // relu(acc + bias) -> one half of x: lane (agent, g) of output tile w holds units 32 w + 8 q + 4 g + 0..3
+    auto hidden_out = [&](const float *bias, int half) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
+                if (a0 + 32 * j + r32 < A.n) *(f32x4 *)(A.x + (size_t)(a0 + 32 * j + r32) * HID + 256 * half + 32 * w + 8 * q + 4 * g) = v;
+            }
+        }
+    };
+    hidden_out(A.bv, 0);
+    // the feature embedding: K = FK (output tile w, four agent tiles)
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
+    for (int m = 0; m < A.FK / 8; m++) {
+        const f32x4 we = A.we[((size_t)m * 8 + w) * 64 + l];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const f32x4 x = *(const f32x4 *)(s_feat + (32 * j + r32) * A.FK + 8 * m + 4 * g);
+            acc[j] = mfma4(we, x, acc[j]);
+        }
+    }
+    hidden_out(A.be, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------- dense 512 and the CommNet step
+constexpr int LY_WAVES = 8, LY_THREADS = 64 * LY_WAVES, LY_TILES = 4, LY_CHUNK = 2;     // groups of 8 K-values a wave has in flight per buffer
+
+struct LayerArgs {
+    const float *in;          // [n][512] x (dense) or h (CommNet step)
+    const float *sum;         // [512] column sums of `in` over the call (CommNet step)
+    const float *skip;        // [n][512] (CommNet step)
+    const f32x4 *w;           // [64 groups][16 tiles][64] (dense) / [128 groups][16 tiles][64]: K = others' 512, then h's 512 (CommNet step)
+    const float *bias;        // [512] (dense)
+    float *out;               // [n][512]
+    int n;
+};
+
+template <bool COMM>
+__global__ void __launch_bounds__(LY_THREADS) k_a2c_layer_f32(LayerArgs A) {
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, g = l >> 5, r32 = l & 31;
+    const int tile0 = (blockIdx.x * LY_WAVES + w) * 32;
+    if (tile0 >= A.n) return;                                    // (whole waves: the MFMAs below see every lane)
+    const int T0 = blockIdx.y * LY_TILES;
+    const int agent = min(tile0 + r32, A.n - 1);
+    const f32x4 *xp = (const f32x4 *)(A.in + (size_t)agent * HID) + g;        // group m: xp[2 m] = in[8 m + 4 g .. + 3]
+    const f32x4 *sp = COMM ? (const f32x4 *)A.sum + g : xp;
+    const f32x4 *wp = A.w + (size_t)T0 * 64 + l;                              // (group m, tile T0 + t) at wp[(m * 16 + t) * 64]
+    const float others_div = (float)(A.n - 1);
+    const bool alone = A.n == 1;
+    f32x16 acc[LY_TILES];
+#pragma unroll
+    for (int t = 0; t < LY_TILES; t++) acc[t] = f32x16{0};
+    f32x4 op[2][LY_CHUNK][2 + LY_TILES];                                      // [buffer][group][row values, column sums, weights]
+    auto phase = [&](auto is_others) __attribute__((always_inline)) {
+        constexpr bool O = decltype(is_others)::value;
+        const f32x4 *wph = wp + ((COMM && !O) ? (size_t)64 * 16 * 64 : 0);
+        auto load = [&](int c, f32x4 (&d)[LY_CHUNK][2 + LY_TILES]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < LY_CHUNK; j++) {
+                const int m = c * LY_CHUNK + j;
+                d[j][0] = xp[2 * m];
+                if (O) d[j][1] = sp[2 * m];
+#pragma unroll
+                for (int t = 0; t < LY_TILES; t++) d[j][2 + t] = wph[((size_t)m * 16 + t) * 64];
+            }
+        };
+        auto run = [&](const f32x4 (&d)[LY_CHUNK][2 + LY_TILES]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < LY_CHUNK; j++) {
+                f32x4 x = d[j][0];
+                if (O) x = alone ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : (d[j][1] - x) / others_div;      // the mean of the OTHER agents
+#pragma unroll
+                for (int t = 0; t < LY_TILES; t++) acc[t] = mfma4(d[j][2 + t], x, acc[t]);
+            }
+        };
+        constexpr int NC = 64 / LY_CHUNK;
+        load(0, op[0]);
+        for (int c = 0; c < NC; c += 2) {
+            load(c + 1, op[1]);
+            run(op[0]);
+            if (c + 2 < NC) load(c + 2, op[0]);
+            run(op[1]);
+        }
+    };
+    if (COMM) phase(std::integral_constant<bool, true>{});
+    phase(std::integral_constant<bool, false>{});
+    // lane (agent, g) holds units u = 32 (T0 + t) + 8 q + 4 g + i in result register 4 q + i of tile t
+    const bool live = tile0 + r32 < A.n;
+#pragma unroll
+    for (int t = 0; t < LY_TILES; t++) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const int u = 32 * (T0 + t) + 8 * q + 4 * g;
+            const f32x4 add = COMM ? *(const f32x4 *)(A.skip + (size_t)agent * HID + u) : *(const f32x4 *)(A.bias + u);
+            f32x4 o;
+#pragma unroll
+            for (int i = 0; i < 4; i++) o[i] = COMM ? tanhf(acc[t][4 * q + i] + add[i]) : relu(acc[t][4 * q + i] + add[i]);
+            if (live) *(f32x4 *)(A.out + (size_t)agent * HID + u) = o;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- column sums in a fixed order
+constexpr int CS_BLOCK = 256;      // agents of a partial sum: block b is agents 256 b .. 256 b + 255 of the call
+
+__global__ void __launch_bounds__(HID) k_a2c_colsum_part_f32(const float *h, int n, float *part) {
+    const int c = threadIdx.x, beg = blockIdx.x * CS_BLOCK, end = min(beg + CS_BLOCK, n);
+    float s = 0.0f;
+#pragma unroll 16
+    for (int a = beg; a < end; a++) s += h[(size_t)a * HID + c];
+    part[(size_t)blockIdx.x * HID + c] = s;
+}
+
+__global__ void __launch_bounds__(HID) k_a2c_colsum_f32(const float *part, int n_blocks, float *sum) {
+    const int c = threadIdx.x;
+    float s = 0.0f;
+#pragma unroll 32
+    for (int b = 0; b < n_blocks; b++) s += part[(size_t)b * HID + c];
+    sum[c] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------- the heads and the draw
+constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES, PH_PITCH = 33;
+
+struct PHeadArgs {
+    const float *h;           // [n][512]
+    const f32x4 *wh;          // [64][64]: K = 512; outputs 0..n_action-1 the policy's, n_action the value's, the rest zero
+    const float *bh;          // [32] per-output biases
+    const float *u;           // [n] uniform in [0, 1)
+    int n, n_action;
+    int *actions;             // [n]
+    float *policy;            // [n][n_action] or null
+    float *value;             // [n] or null
+};
+
+__global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
+    __shared__ float s_p[PH_WAVES * 32 * PH_PITCH];               // the probability rows of the workgroup's agents
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6, g = l >> 5, r32 = l & 31;
+    const int tile0 = (blockIdx.x * PH_WAVES + w) * 32;
+    const int agent = min(tile0 + r32, A.n - 1);                 // (waves past n repeat the last agent and store nothing)
+    const bool live = tile0 + r32 < A.n;
+    const f32x4 *hp = (const f32x4 *)(A.h + (size_t)agent * HID) + g;
+    f32x16 acc = {0};
+    f32x4 hw[2], hx[2];
+    hw[0] = A.wh[l];
+    hx[0] = hp[0];
+    for (int m = 0; m < HID / 8; m++) {
+        if (m + 1 < HID / 8) { hw[(m + 1) & 1] = A.wh[(m + 1) * 64 + l]; hx[(m + 1) & 1] = hp[2 * (m + 1)]; }
+        acc = mfma4(hw[m & 1], hx[m & 1], acc);
+    }
+    // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] += A.bh[(r & 3) + 8 * (r >> 2) + 4 * g];
+    float top = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        if (o < A.n_action) top = fmaxf(top, acc[r]);            // (a NaN is passed over here and reaches the sum through its own exp)
+    }
+    top = fmaxf(top, __shfl_xor(top, 32));
+    float e[16], sum = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        e[r] = o < A.n_action ? expf(acc[r] - top) : 0.0f;
+        sum += e[r];
+    }
+    sum += __shfl_xor(sum, 32);
+    float *row = s_p + (w * 32 + r32) * PH_PITCH;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        float p = e[r] / sum;
+        p = p < 1e-10f ? 1e-10f : (p > (float)(1.0 - 1e-10) ? (float)(1.0 - 1e-10) : p);      // torch.clamp: a NaN stays
+        if (o < A.n_action) {
+            row[o] = p;
+            if (live && A.policy) A.policy[(size_t)agent * A.n_action + o] = p;
+        }
+        if (o == A.n_action && live && A.value) A.value[agent] = acc[r];
+    }
+    __syncthreads();
+    if (g == 0 && live) {
+        float c = row[0];
+        for (int a = 1; a < A.n_action; a++) c += row[a];
+        const float t = A.u[agent] * c;
+        int act = A.n_action - 1;                                // (no c_a > t: rounding, or a NaN in the row)
+        c = row[0];
+        for (int a = 0; a < A.n_action - 1; a++) {
+            if (c > t) { act = a; break; }
+            c += row[a + 1];
+        }
+        A.actions[agent] = act;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- the workspace
+struct Layout { size_t x, h0, h1, part, sum, bytes; int n_blocks; };
+static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+static Layout layout(int n, bool comm) {
+    Layout L{};
+    const size_t rows = up256((size_t)n * HID * sizeof(float));
+    L.n_blocks = (n + CS_BLOCK - 1) / CS_BLOCK;
+    L.x = 0; L.h0 = rows; L.bytes = 2 * rows;
+    if (comm) {
+        L.h1 = L.bytes; L.part = L.h1 + rows; L.sum = L.part + up256((size_t)L.n_blocks * HID * sizeof(float));
+        L.bytes = L.sum + HID * sizeof(float);
+    }
+    return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int policy_a2c_f32_supported(const PolicyDqnShape *s) {
+    return s->view_h >= 1 && s->view_w >= 1 && s->view_c >= 1 && (long long)s->view_h * s->view_w * s->view_c <= TR_KMAX && s->feat >= 1 &&
+           s->feat <= TR_FMAX && s->n_action >= 1 && s->n_action <= 31;
+}
+
+int policy_a2c_f32_workspace_bytes(const PolicyDqnShape *s, int n, int use_comm, size_t *bytes) {
+    (void)s;
+    *bytes = layout(n < 0 ? 0 : n, use_comm != 0).bytes;
+    return 0;
+}
+
+int policy_a2c_infer_f32(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, const float *view, const float *feat, int n, const float *u,
+                         void *workspace, int *actions, float *policy, float *value, void *stream) {
+    if (!s || !w || !policy_a2c_f32_supported(s)) return 1;
+    const bool comm = w->use_comm != 0;
+    if (!w->dense_view || !w->dense_emb || !w->dense || !w->head || !w->dense_view_bias || !w->dense_emb_bias || !w->dense_bias || !w->head_bias) return 1;
+    if (comm && !(w->comm[0] && w->comm[1])) return 1;
+    if (n <= 0) return 0;
+    if (!view || !feat || !u || !actions || !workspace) return 1;
+    if ((uintptr_t)workspace & 15) return 1;                     // (rows are read and written as float4)
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0, caller_dev = -1;
+    if (hipGetDevice(&caller_dev) != hipSuccess) return 2;
+    if (st) { if (hipStreamGetDevice(st, &dev) != hipSuccess || hipSetDevice(dev) != hipSuccess) return 2; }
+    else dev = caller_dev;
+    struct Restore { int d, cur; ~Restore() { if (d != cur) (void)hipSetDevice(d); } } restore{caller_dev, dev};
+    constexpr int MAX_DEV = 64;
+    if (dev < 0 || dev >= MAX_DEV) return 2;
+    static bool lds_ok_dev[MAX_DEV] = {};
+    if (!lds_ok_dev[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_a2c_trunk_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TR_LDS) != hipSuccess) return 2;
+        lds_ok_dev[dev] = true;
+    }
+    const Layout L = layout(n, comm);
+    char *ws = (char *)workspace;
+    float *x = (float *)(ws + L.x), *h0 = (float *)(ws + L.h0);
+    TrunkArgs T{};
+    T.view = view; T.feat = feat; T.wv = (const f32x4 *)w->dense_view; T.we = (const f32x4 *)w->dense_emb; T.bv = w->dense_view_bias; T.be = w->dense_emb_bias;
+    T.n = n; T.K = s->view_h * s->view_w * s->view_c; T.KG = (T.K + 7) / 8; T.F = s->feat; T.FK = (s->feat + 7) / 8 * 8; T.x = x;
+    hipLaunchKernelGGL(k_a2c_trunk_f32, dim3((n + TR_M - 1) / TR_M), dim3(TR_THREADS), TR_LDS, st, T);
+    const dim3 lgrid((n + 32 * LY_WAVES - 1) / (32 * LY_WAVES), HID / 32 / LY_TILES);
+    LayerArgs D{};
+    D.in = x; D.w = (const f32x4 *)w->dense; D.bias = w->dense_bias; D.out = h0; D.n = n;
+    hipLaunchKernelGGL(k_a2c_layer_f32<false>, lgrid, dim3(LY_THREADS), 0, st, D);
+    const float *h = h0;
+    if (comm) {
+        float *part = (float *)(ws + L.part), *sum = (float *)(ws + L.sum);
+        float *outs[2] = {x, (float *)(ws + L.h1)};              // (x is free once the dense layer has read it)
+        for (int step = 0; step < 2; step++) {
+            hipLaunchKernelGGL(k_a2c_colsum_part_f32, dim3(L.n_blocks), dim3(HID), 0, st, h, n, part);
+            hipLaunchKernelGGL(k_a2c_colsum_f32, dim3(1), dim3(HID), 0, st, (const float *)part, L.n_blocks, sum);
+            LayerArgs C{};
+            C.in = h; C.sum = sum; C.skip = h0; C.w = (const f32x4 *)w->comm[step]; C.out = outs[step]; C.n = n;
+            hipLaunchKernelGGL(k_a2c_layer_f32<true>, lgrid, dim3(LY_THREADS), 0, st, C);
+            h = outs[step];
+        }
+    }
+    PHeadArgs P{};
+    P.h = h; P.wh = (const f32x4 *)w->head; P.bh = w->head_bias; P.u = u; P.n = n; P.n_action = s->n_action;
+    P.actions = actions; P.policy = policy; P.value = value;
+    hipLaunchKernelGGL(k_a2c_head_f32, dim3((n + 32 * PH_WAVES - 1) / (32 * PH_WAVES)), dim3(PH_THREADS), 0, st, P);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+}  // extern "C"
