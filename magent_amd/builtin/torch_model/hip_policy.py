@@ -3,7 +3,9 @@ magent_amd/csrc/policy.hip) to the PyTorch model that owns the parameters (dqn.p
 
 The kernels want every weight matrix in the operand order of v_mfma_f32_32x32x16_bf16 ("fragment order") and every
 activation in the order a lane of the MFMA result holds its 16 outputs ("slot order"); both are plain index permutations of
-the torch parameters, done here with tensor ops on the device whenever the parameters have changed."""
+the torch parameters, done here with tensor ops on the device whenever the parameters have changed: every policy notices by itself that a
+parameter was written or replaced since it packed (_SourceStamp), whoever did it -- train(), load(), load_state_dict, an optimiser of
+the caller's.  Setting `.dirty = True` forces a repack."""
 import ctypes
 
 import torch
@@ -38,11 +40,46 @@ def fragment_order(w):
 CONV1_TAP_ORDER = [0, 3, 1, 4, 2, 5, 6, 7, 8, 9]       # tap (ky * 3 + kx; 9 = padding) in position 2 s + g of conv1's reduction index
 
 
+class _SourceStamp(object):
+    """What a packed copy of a module's parameters was made from: every parameter's storage address and version counter.
+
+    The packed copy is stale when a parameter has been written in place (an optimiser step, load_state_dict, copy_, add_: each bumps the
+    tensor's `_version`) or replaced (`.to()`, `.float()`, a new nn.Parameter: another storage address).  The stamp holds the parameters'
+    tensors (detached views of the same storage), so a replaced storage stays allocated until the next pack and its address cannot come
+    back under a new tensor.  Not seen: a write through `p.data` (it bypasses the version counter) -- the `dirty` flag is for that."""
+    __slots__ = ("tensors", "slots")
+
+    def __init__(self, module):
+        self.tensors, self.slots = [], []        # slots: (the owning module's parameter dict, name, address, version) -- no tree walk per call
+        for m in module.modules():
+            for name, p in m._parameters.items():
+                if p is not None:
+                    t = p.detach()
+                    self.tensors.append(t)
+                    self.slots.append((m._parameters, name, t.data_ptr(), t._version))
+
+    def differs(self, module):
+        for params, name, address, version in self.slots:
+            p = params.get(name)
+            if p is None or p.data_ptr() != address or p._version != version:
+                return True
+        return False
+
+
+class _Packed(object):
+    """a policy that keeps a packed copy of its module's parameters (`_source` names the attribute that holds the module)"""
+    _source = "qnet"
+
+    def stale(self):
+        """does the packed copy have to be rebuilt before the next kernel call?  (a dozen address / counter reads per call)"""
+        return self.dirty or self._stamp is None or self._stamp.differs(getattr(self, self._source))
+
+
 def _pad_k(w, k):
     return torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], dim=1) if w.shape[1] < k else w
 
 
-class HipDqnPolicy(object):
+class HipDqnPolicy(_Packed):
     """greedy actions (and, for tests, the Q values) of a dueling conv _QNet, computed by k_dqn_conv + k_dqn_head"""
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072):
@@ -53,12 +90,13 @@ class HipDqnPolicy(object):
         if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP policy kernels")
         self.k_dense = (h - 4) * (w - 4) * 32
-        self._packed, self._work = None, None
-        self.dirty = True
+        self._packed, self._work, self._stamp = None, None, None
+        self.dirty = True      # (set by a caller: repack whatever the stamp says)
 
     @torch.no_grad()
     def pack(self):
         q, dev = self.qnet, self.device
+        stamp = _SourceStamp(q)
         ch = slot_channels(dev)
         c = self.shape.view_c
         w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
@@ -85,7 +123,7 @@ class HipDqnPolicy(object):
         for k, v in t.items():
             setattr(w, k, v.data_ptr())
         w.value_bias = float(q.value.bias.detach().float().item())
-        self._packed, self._w, self.dirty = t, w, False       # (the tensors stay alive as long as the pointers are in use)
+        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False       # (the tensors stay alive as long as the pointers are in use)
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -95,7 +133,7 @@ class HipDqnPolicy(object):
         assert view.is_cuda and view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32
         assert (cells16 and view.shape[-1] == 8) or (view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c)
         call = self._lib.policy_dqn_infer_bf16 if cells16 else self._lib.policy_dqn_infer
-        if self.dirty:
+        if self.stale():
             self.pack()
         n = view.shape[0]
         actions = torch.empty(n, dtype=torch.int32, device=view.device)
@@ -143,7 +181,7 @@ def _trunk_f32(q, shape, dev):
     }
 
 
-class HipDqnPolicyF32(object):
+class HipDqnPolicyF32(_Packed):
     """greedy actions (and the Q values) of a dueling conv _QNet in float32 -- inputs, weights, activations, accumulation: the reference
     network's own arithmetic -- computed by k_dqn_conv_f32 + k_dqn_head_f32 on v_mfma_f32_32x32x2_f32 (magent_amd/csrc/policy_f32.hip)"""
 
@@ -155,12 +193,13 @@ class HipDqnPolicyF32(object):
         if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 policy kernels")
         self.k_dense = (h - 4) * (w - 4) * 32
-        self._packed, self._work = None, None
-        self.dirty = True
+        self._packed, self._work, self._stamp = None, None, None
+        self.dirty = True      # (set by a caller: repack whatever the stamp says)
 
     @torch.no_grad()
     def pack(self):
         q, dev = self.qnet, self.device
+        stamp = _SourceStamp(q)
         t = _trunk_f32(q, self.shape, dev)
         head = torch.zeros(32, 512, device=dev)
         head[:self.shape.n_action] = q.advantage.weight.detach().float()
@@ -170,7 +209,7 @@ class HipDqnPolicyF32(object):
         for k, v in t.items():
             setattr(w, k, v.data_ptr())
         w.value_bias = float(q.value.bias.detach().float().item())
-        self._packed, self._w, self.dirty = t, w, False
+        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -178,7 +217,7 @@ class HipDqnPolicyF32(object):
         Returns int32 actions [n] (and Q [n][A])"""
         assert view.is_cuda and view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
         assert view.shape[-1] == self.shape.view_c
-        if self.dirty:
+        if self.stale():
             self.pack()
         n = view.shape[0]
         actions = torch.empty(n, dtype=torch.int32, device=view.device)
@@ -203,7 +242,7 @@ class _DrqnWeights(ctypes.Structure):
                 ("head", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("dueling", ctypes.c_int)]
 
 
-class HipDrqnPolicyF32(object):
+class HipDrqnPolicyF32(_Packed):
     """one acting step of a _RecurrentQNet in float32 -- the DQN's trunk (k_dqn_conv_f32 + k_dqn_head_f32), a GRU(512) cell (k_drqn_gru_f32),
     the head and argmax (k_drqn_head_f32): magent_amd/csrc/policy_drqn_f32.hip -- and the GRU state of every agent id in device memory.
 
@@ -220,8 +259,8 @@ class HipDrqnPolicyF32(object):
         self.shape = _Shape(h, w, c, feature_space[0], n_action)
         if qnet.rnn.hidden_size != self.STATE or not self._lib.policy_drqn_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 DRQN kernels")
-        self._packed, self._work = None, None
-        self.dirty = True
+        self._packed, self._work, self._stamp = None, None, None
+        self.dirty = True      # (set by a caller: repack whatever the stamp says)
         self.clear()
 
     # ---- the state table
@@ -252,6 +291,7 @@ class HipDrqnPolicyF32(object):
     @torch.no_grad()
     def pack(self):
         q, dev, S, A = self.qnet, self.device, self.STATE, self.shape.n_action
+        stamp = _SourceStamp(q)
         t = _trunk_f32(q, self.shape, dev)
         rnn = q.rnn
         wih, whh = rnn.weight_ih_l0.detach().float(), rnn.weight_hh_l0.detach().float()        # [3 S][S], gates r, z, n
@@ -278,7 +318,7 @@ class HipDrqnPolicyF32(object):
         for k in ("gru", "gru_bias", "gru_bias0", "head", "head_bias"):
             setattr(w, k, t[k].data_ptr())
         w.dueling = int(bool(q.use_dueling))
-        self._packed, self._w, self.dirty = t, w, False
+        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False
 
     # ---- one step
     @torch.no_grad()
@@ -288,7 +328,7 @@ class HipDrqnPolicyF32(object):
         assert view.device == feature.device == ids.device and view.device.type == self.device.type
         assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
         assert view.shape[-1] == self.shape.view_c and ids.dtype == torch.int32 and view.shape[0] == feature.shape[0] == ids.shape[0]
-        if self.dirty:
+        if self.stale():
             self.pack()
         n, dev = view.shape[0], view.device
         ids = ids.clone(memory_format=torch.contiguous_format)        # (the table keeps it: the caller's buffer may be reused)
@@ -320,7 +360,7 @@ class _A2cWeights(ctypes.Structure):
                 ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
 
 
-class HipA2cPolicyF32(object):
+class HipA2cPolicyF32(_Packed):
     """one acting step of an _ActorCritic in float32 -- the two input layers (k_a2c_trunk_f32), dense 512 and the two CommNet steps
     (k_a2c_layer_f32, the column sums by k_a2c_colsum_part_f32 + k_a2c_colsum_f32), the policy and value heads, the softmax and the draw
     (k_a2c_head_f32): magent_amd/csrc/policy_a2c_f32.hip.
@@ -331,6 +371,8 @@ class HipA2cPolicyF32(object):
     in the same order, and the result does not depend on `chunk`.  `lib`: a library other than the product's (the tests' emulated build;
     its "device" memory is the host's, so the tensors are CPU tensors)."""
 
+    _source = "net"
+
     def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
         self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
         self.net, self.device, self.chunk = net, torch.device(device), int(chunk)
@@ -339,12 +381,13 @@ class HipA2cPolicyF32(object):
         self.use_comm = net.comm is not None
         if net.dense.in_features != 512 or net.dense.out_features != 512 or not self._lib.policy_a2c_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 A2C kernels")
-        self._packed, self._work = None, None
-        self.dirty = True
+        self._packed, self._work, self._stamp = None, None, None
+        self.dirty = True      # (set by a caller: repack whatever the stamp says)
 
     @torch.no_grad()
     def pack(self):
         net, dev, A = self.net, self.device, self.shape.n_action
+        stamp = _SourceStamp(net)
         wv = net.dense_view.weight.detach().float()
         t = {
             "dense_view": fragment_order_f32(_pad_k(wv, (wv.shape[1] + 7) // 8 * 8)),
@@ -366,7 +409,7 @@ class HipA2cPolicyF32(object):
                 t["comm%d" % s] = fragment_order_f32(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
                 w.comm[s] = t["comm%d" % s].data_ptr()
         w.use_comm = int(self.use_comm)
-        self._packed, self._w, self.dirty = t, w, False       # (the tensors stay alive as long as the pointers are in use)
+        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False       # (the tensors stay alive as long as the pointers are in use)
 
     @torch.no_grad()
     def infer(self, view, feature, u=None, want_policy=False, want_value=False):
@@ -376,7 +419,7 @@ class HipA2cPolicyF32(object):
         assert view.device == feature.device and view.device.type == self.device.type
         assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
         assert tuple(view.shape[1:]) == (self.shape.view_h, self.shape.view_w, self.shape.view_c) and view.shape[0] == feature.shape[0]
-        if self.dirty:
+        if self.stale():
             self.pack()
         n, dev, A = view.shape[0], view.device, self.shape.n_action
         if u is None:

@@ -1504,3 +1504,203 @@ def f32_error_bound(view_space, feat, n_action):
     h, w, _ = view_space
     fk = (feat + 7) // 8 * 8
     return (72 + 1) + (288 + 1) + ((h - 4) * (w - 4) * 32 + 1) + (fk + 1) + 512 + (n_action + 4)
+
+
+# ---------------------------------------------------------------------------------------------------- the DRQN and the A2C networks in float64
+def _sd64(module):
+    return {k: v.detach().cpu().double().numpy() for k, v in module.state_dict().items()}
+
+
+def rqnet_tf_params(qnet):
+    """a _RecurrentQNet's parameters in TensorFlow's layout (tf_model/drqn.py:140-187), float64.  The trunk as qnet_tf_params.  The GRU as
+    tf.contrib.rnn.GRUCell (drqn.py:168) keeps it: `gates/kernel` [x | h stacked on the input axis: 1024][r | u: 1024], `gates/bias` [1024],
+    `candidate/kernel` [x | h: 1024][512], `candidate/bias` [512]; torch keeps weight_ih / weight_hh [r | z | n: 1536][512] and two bias
+    vectors.  The gates' two biases add up to one; the candidate's recurrent bias b_hn has no counterpart in the reference's cell and is
+    kept apart as `candidate/recurrent_bias` (np_rqnet says where each convention adds it).  Heads: `dense_value`, `dense_advantage`
+    (no bias) for the dueling network (drqn.py:178-180), `dense` for the plain one (drqn.py:184)."""
+    sd, S = _sd64(qnet), qnet.STATE
+    wih, whh, bih, bhh = sd["rnn.weight_ih_l0"], sd["rnn.weight_hh_l0"], sd["rnn.bias_ih_l0"], sd["rnn.bias_hh_l0"]
+    p = {"conv1/kernel": sd["conv1.weight"].transpose(2, 3, 1, 0), "conv1/bias": sd["conv1.bias"],
+         "conv2/kernel": sd["conv2.weight"].transpose(2, 3, 1, 0), "conv2/bias": sd["conv2.bias"],
+         "dense_view/kernel": sd["dense_view.weight"].T, "dense_view/bias": sd["dense_view.bias"],
+         "dense_emb/kernel": sd["dense_emb.weight"].T, "dense_emb/bias": sd["dense_emb.bias"],
+         "gru_cell/gates/kernel": np.concatenate([wih[:2 * S].T, whh[:2 * S].T], axis=0), "gru_cell/gates/bias": bih[:2 * S] + bhh[:2 * S],
+         "gru_cell/candidate/kernel": np.concatenate([wih[2 * S:].T, whh[2 * S:].T], axis=0), "gru_cell/candidate/bias": bih[2 * S:],
+         "gru_cell/candidate/recurrent_bias": bhh[2 * S:]}
+    if qnet.use_dueling:
+        p.update({"dense_value/kernel": sd["value.weight"].T, "dense_value/bias": sd["value.bias"], "dense_advantage/kernel": sd["advantage.weight"].T})
+    else:
+        p.update({"dense/kernel": sd["value.weight"].T, "dense/bias": sd["value.bias"]})
+    return p
+
+
+def np_rqnet(params, view, feature, batch, unroll, state=None, use_dueling=True, reset_after=False, dueling_reads="rnn", dtype=np.float64):
+    """NumPy restatement of the reference's recurrent network (tf_model/drqn.py:140-187) -> (Q [batch * unroll][A], state [batch][512]).
+    `params` in TensorFlow's layout (rqnet_tf_params); view / feature hold batch * unroll rows, a batch entry's steps one after another
+    (drqn.py:170: reshape to [batch, unroll, 512]); `state` None: zeros (drqn.py:171).
+
+    Trunk (drqn.py:153-164): as np_qnet.  GRU (drqn.py:168-174), the two conventions side by side:
+      reset_after=False -- tf.contrib.rnn.GRUCell, the reference's cell:  [r | u] = sigmoid([x, h] W_g + b_g);
+                           c = tanh([x, r * h] W_c + b_c);  h' = u * h + (1 - u) * c.  (b_c here is candidate/bias + candidate/recurrent_bias:
+                           one bias vector, as that cell has; TensorFlow initialises b_g to 1, torch draws it like the weights.)
+      reset_after=True  -- torch.nn.GRU (and cuDNN / MIOpen, Keras' reset_after=True): the same gates;
+                           c = tanh(x W_cx + b_c + r * (h W_ch + b_rc));  the same h'.
+    Head: the plain one reads the GRU's output (drqn.py:184).  The dueling one, as the reference writes it, reads `dense`, the GRU's INPUT
+    (drqn.py:178-179): dueling_reads="dense".  dueling_reads="rnn" reads the GRU's output like the plain head (ours does)."""
+    P = {k: np.asarray(v, dtype=np.float64).astype(dtype) for k, v in params.items()}
+    S = P["gru_cell/candidate/kernel"].shape[1]
+    relu = lambda a: np.maximum(a, 0)
+    sigmoid = lambda a: 1.0 / (1.0 + np.exp(-a))
+
+    def conv_valid(x, k, b):
+        n, h, w, c = x.shape
+        out = np.zeros((n, h - 2, w - 2, k.shape[3]), dtype=dtype)
+        for dy in range(3):
+            for dx in range(3):
+                out += np.tensordot(x[:, dy:dy + h - 2, dx:dx + w - 2, :], k[dy, dx], axes=([3], [0])).astype(dtype)
+        return relu(out + b)
+    x = np.asarray(view, dtype=np.float64).astype(dtype)
+    f = np.asarray(feature, dtype=np.float64).astype(dtype)
+    h2 = conv_valid(conv_valid(x, P["conv1/kernel"], P["conv1/bias"]), P["conv2/kernel"], P["conv2/bias"])
+    flat = h2.reshape(h2.shape[0], -1)
+    dense = np.concatenate([relu(flat @ P["dense_view/kernel"] + P["dense_view/bias"]), relu(f @ P["dense_emb/kernel"] + P["dense_emb/bias"])], axis=1)
+    seq = dense.reshape(batch, unroll, S)
+    h = np.zeros((batch, S), dtype=dtype) if state is None else np.asarray(state, dtype=np.float64).astype(dtype).reshape(batch, S)
+    Wg, bg, Wc = P["gru_cell/gates/kernel"], P["gru_cell/gates/bias"], P["gru_cell/candidate/kernel"]
+    bc, brc = P["gru_cell/candidate/bias"], P["gru_cell/candidate/recurrent_bias"]
+    outs = []
+    for t in range(unroll):
+        xt = seq[:, t]
+        g = sigmoid(np.concatenate([xt, h], axis=1) @ Wg + bg)
+        r, u = g[:, :S], g[:, S:]
+        if reset_after:
+            c = np.tanh(xt @ Wc[:S] + bc + r * (h @ Wc[S:] + brc))
+        else:
+            c = np.tanh(np.concatenate([xt, r * h], axis=1) @ Wc + (bc + brc))
+        h = u * h + (1 - u) * c
+        outs.append(h)
+    rnn = np.stack(outs, axis=1).reshape(batch * unroll, S)
+    if not use_dueling:
+        return rnn @ P["dense/kernel"] + P["dense/bias"], h
+    top = {"rnn": rnn, "dense": dense}[dueling_reads]
+    adv = top @ P["dense_advantage/kernel"]
+    return top @ P["dense_value/kernel"] + P["dense_value/bias"] + adv - adv.mean(axis=1, keepdims=True), h
+
+
+def actor_critic_tf_params(net):
+    """an _ActorCritic's parameters in TensorFlow's layout (tf_model/a2c.py:94-161), float64, under the names TensorFlow gives the unnamed
+    layers in the order a2c.py creates them: dense (view), dense_1 (feature), dense_2 (512), step_0_C / _H, step_1_C / _H (the CommNet
+    block multiplies from the right, a2c.py:102: [in, out]), dense_3 (policy), dense_4 (value)"""
+    sd = _sd64(net)
+    p = {}
+    for tf_name, ours in (("dense", "dense_view"), ("dense_1", "dense_emb"), ("dense_2", "dense"), ("dense_3", "policy"), ("dense_4", "value")):
+        p[tf_name + "/kernel"], p[tf_name + "/bias"] = sd[ours + ".weight"].T, sd[ours + ".bias"]
+    if net.comm is not None:
+        for s in range(2):
+            p["step_%d_C" % s], p["step_%d_H" % s] = sd["comm.%d.C.weight" % s].T, sd["comm.%d.H.weight" % s].T
+    return p
+
+
+def np_actor_critic(params, view, feature, use_comm, dtype=np.float64):
+    """NumPy restatement of the reference's actor-critic (tf_model/a2c.py:76-162) -> (policy [n][A], value [n]); `params` in TensorFlow's
+    layout (actor_critic_tf_params); num_agent = the number of rows, as infer_action and train feed it (a2c.py:213, 282).
+    Flattened view -> dense 256 relu || dense 256 relu on the features -> concat -> dense 512 relu (a2c.py:148-154); the CommNet block as
+    a2c.py:94-102 writes it: mask = (ones - eye) * (1 / (n - 1) if n > 1 else 0), message = mask @ hidden,
+    tanh(message C + hidden H + skip), twice, skip = the dense layer's output both times (a2c.py:120-124); softmax, then
+    clip_by_value(1e-10, 1 - 1e-10) (a2c.py:159-160); value = dense 1 on the same hidden units (a2c.py:161-162)."""
+    P = {k: np.asarray(v, dtype=np.float64).astype(dtype) for k, v in params.items()}
+    relu = lambda a: np.maximum(a, 0)
+    n = len(view)
+    flat = np.asarray(view, dtype=np.float64).astype(dtype).reshape(n, -1)
+    f = np.asarray(feature, dtype=np.float64).astype(dtype)
+    dense = np.concatenate([relu(flat @ P["dense/kernel"] + P["dense/bias"]), relu(f @ P["dense_1/kernel"] + P["dense_1/bias"])], axis=1)
+    dense = relu(dense @ P["dense_2/kernel"] + P["dense_2/bias"])
+    if use_comm:
+        mask = (np.ones((n, n), dtype=dtype) - np.eye(n, dtype=dtype)) * dtype(1.0 / (n - 1.0) if n > 1 else 0.0)
+        skip, h = dense, dense
+        for s in range(2):
+            h = np.tanh((mask @ h) @ P["step_%d_C" % s] + h @ P["step_%d_H" % s] + skip)
+        dense = h
+    logits = dense @ P["dense_3/kernel"] + P["dense_3/bias"]
+    e = np.exp(logits - logits.max(axis=1, keepdims=True))
+    policy = np.clip(e / e.sum(axis=1, keepdims=True), dtype(1e-10), dtype(1 - 1e-10))
+    return policy, (dense @ P["dense_4/kernel"] + P["dense_4/bias"]).reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------------- one training step in float64
+def np_q_target(t_q, q, rewards, terminal, gamma, use_double):
+    """tf_model/dqn.py:233-248 = drqn.py:247-277: the target network's value of the successor at the online network's greedy action
+    (double DQN) or its own maximum; terminal transitions take the reward alone"""
+    n = len(rewards)
+    nxt = t_q[np.arange(n), np.argmax(q, axis=1)] if use_double else t_q.max(axis=1)
+    return np.where(terminal, rewards, rewards + gamma * nxt)
+
+
+def np_masked_td_loss(target, q, action, mask):
+    """dqn.py:105-107 = drqn.py:102-107 -> (loss, dloss/dq): sum(mask * (target - q[i, action_i])^2) / sum(mask)"""
+    n = len(target)
+    td = target - q[np.arange(n), action]
+    grad = np.zeros_like(q)
+    grad[np.arange(n), action] = -2.0 * td * mask / mask.sum()
+    return float((td ** 2 * mask).sum() / mask.sum()), grad
+
+
+def np_drqn_window(item_terminal, start, unroll):
+    """drqn.py:360-372: the rows of an episode a window takes and its mask -> (real steps, mask [real]): every taken step counts, except
+    the last one when the episode goes on behind it (its successor is not in the window)"""
+    real = min(len(item_terminal) - start, unroll)
+    mask = np.ones(real)
+    if not item_terminal[start + real - 1]:
+        mask[real - 1] = 0
+    return real, mask
+
+
+def np_discounted_returns(rewards, bootstrap, gamma):
+    """a2c.py:257-265: keep = V(last observation); for i from the end: keep = keep * gamma + r[i]"""
+    out, keep = np.zeros(len(rewards)), float(bootstrap)
+    for i in reversed(range(len(rewards))):
+        keep = keep * gamma + float(rewards[i])
+        out[i] = keep
+    return out
+
+
+def np_a2c_losses(policy, value, action, returns, value_coef, ent_coef):
+    """a2c.py:163-172 -> (pg_loss, vf_loss, neg_entropy) with log(policy + 1e-6); the advantage is a constant of the gradient"""
+    n = len(action)
+    log_policy = np.log(policy + 1e-6)
+    advantage = returns - value
+    pg = -np.mean(advantage * log_policy[np.arange(n), action])
+    vf = value_coef * np.mean((returns - value) ** 2)
+    ent = ent_coef * np.mean((policy * log_policy).sum(axis=1))
+    return float(pg), float(vf), float(ent)
+
+
+def np_clip_by_global_norm(grads, clip):
+    """tf.clip_by_global_norm (dqn.py:112, drqn.py:112): every gradient times clip / max(global norm, clip) -> (grads, global norm)"""
+    norm = float(np.sqrt(sum(float((g ** 2).sum()) for g in grads)))
+    return [g * (clip / max(norm, clip)) for g in grads], norm
+
+
+class NpAdam(object):
+    """Adam (Kingma & Ba, algorithm 1; lr, 0.9, 0.999, 1e-8: the defaults of tf.train.AdamOptimizer and torch.optim.Adam) in float64.
+    TensorFlow folds the bias corrections into the step size and so adds its epsilon to sqrt(v), not sqrt(v-hat): at step t that is an
+    epsilon of 1e-8 / sqrt(1 - 0.999^t) in this form -- at most 3.2e-7, seen only by gradients that small."""
+
+    def __init__(self, lr, b1=0.9, b2=0.999, eps=1e-8):
+        self.lr, self.b1, self.b2, self.eps, self.t, self.m, self.v = lr, b1, b2, eps, 0, None, None
+
+    def update(self, grads):
+        """(the steps to ADD to the parameters for these gradients, the same steps with the first moment's two terms taken as magnitudes:
+        what a rounding error of the float32 optimiser is relative to where b1 m and (1 - b1) g cancel)"""
+        if self.m is None:
+            self.m, self.v = [np.zeros_like(g) for g in grads], [np.zeros_like(g) for g in grads]
+        self.t += 1
+        out, mags = [], []
+        for i, g in enumerate(grads):
+            mag = self.b1 * np.abs(self.m[i]) + (1 - self.b1) * np.abs(g)
+            self.m[i] = self.b1 * self.m[i] + (1 - self.b1) * g
+            self.v[i] = self.b2 * self.v[i] + (1 - self.b2) * g * g
+            mhat, vhat = self.m[i] / (1 - self.b1 ** self.t), self.v[i] / (1 - self.b2 ** self.t)
+            out.append(-self.lr * mhat / (np.sqrt(vhat) + self.eps))
+            mags.append(self.lr * mag / (1 - self.b1 ** self.t) / (np.sqrt(vhat) + self.eps))
+        return out, mags
