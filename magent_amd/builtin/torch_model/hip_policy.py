@@ -67,12 +67,66 @@ class _SourceStamp(object):
 
 
 class _Packed(object):
-    """a policy that keeps a packed copy of its module's parameters (`_source` names the attribute that holds the module)"""
+    """a policy that keeps a packed copy of its module's parameters (`_source` names the attribute that holds the module) and a workspace
+    for the library's calls.  `lib`: a library other than the product's (the tests' emulated build; its "device" memory is the host's,
+    so the tensors are CPU tensors)."""
     _source = "qnet"
+
+    def __init__(self, module, view_space, feature_space, n_action, device, chunk, lib=None):
+        self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
+        setattr(self, self._source, module)
+        self.device, self.chunk = torch.device(device), int(chunk)
+        h, w, c = view_space
+        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        self._packed, self._work, self._stamp = None, None, None
+        self.dirty = True      # (set by a caller: repack whatever the stamp says)
 
     def stale(self):
         """does the packed copy have to be rebuilt before the next kernel call?  (a dozen address / counter reads per call)"""
         return self.dirty or self._stamp is None or self._stamp.differs(getattr(self, self._source))
+
+    def _set_packed(self, tensors, weights, stamp):
+        """(the tensors stay alive as long as the pointers are in use)"""
+        self._packed, self._w, self._stamp, self.dirty = tensors, weights, stamp, False
+
+    def _grow_work(self, device, bytes_fn, *args):
+        """the workspace on `device`, at least as large as the library's `bytes_fn(shape, *args)` reports"""
+        nbytes = ctypes.c_size_t(0)
+        bytes_fn(ctypes.byref(self.shape), *args, ctypes.byref(nbytes))
+        if self._work is None or self._work.numel() < nbytes.value:
+            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=device)
+
+    def _chunked(self, name, n, chunk, call):
+        """call(beg, m) -> the library's return code, for every chunk of at most `chunk` of the n agents"""
+        for beg in range(0, n, max(chunk, 1)):
+            rc = call(beg, min(chunk, n - beg))
+            if rc != 0:
+                raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def _stream(device):
+    """torch's current stream on a CUDA device; None (the null stream) for the emulated library's CPU tensors"""
+    return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _set_pointers(struct, tensors, keys=None):
+    """the addresses of `tensors` (a dict; `keys`: some of it) into the same-named fields of a ctypes struct"""
+    for k in (tensors if keys is None else keys):
+        setattr(struct, k, tensors[k].data_ptr())
+
+
+def _head_32x512(rows, device, biases=()):
+    """the padded head [32][512] (and its bias [32]) from (first output row, weight [r][512]) pairs (and (first row, bias [r]) pairs)"""
+    head, hb = torch.zeros(32, 512, device=device), torch.zeros(32, device=device)
+    for at, w in rows:
+        head[at:at + w.shape[0]] = w.detach().float()
+    for at, b in biases:
+        hb[at:at + b.shape[0]] = b.detach().float()
+    return head, hb
 
 
 def _pad_k(w, k):
@@ -83,15 +137,10 @@ class HipDqnPolicy(_Packed):
     """greedy actions (and, for tests, the Q values) of a dueling conv _QNet, computed by k_dqn_conv + k_dqn_head"""
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072):
-        self._lib = c_lib.load()
-        self.qnet, self.device, self.chunk = qnet, torch.device(device), int(chunk)
-        h, w, c = view_space
-        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        super().__init__(qnet, view_space, feature_space, n_action, device, chunk)
         if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP policy kernels")
-        self.k_dense = (h - 4) * (w - 4) * 32
-        self._packed, self._work, self._stamp = None, None, None
-        self.dirty = True      # (set by a caller: repack whatever the stamp says)
+        self.k_dense = (view_space[0] - 4) * (view_space[1] - 4) * 32
 
     @torch.no_grad()
     def pack(self):
@@ -109,9 +158,7 @@ class HipDqnPolicy(_Packed):
         fk = (self.shape.feat + 15) // 16 * 16
         we = _pad_k(q.dense_emb.weight.detach().float(), fk)
         hidden = (torch.arange(16, device=dev)[:, None] * 32 + ch[None, :]).reshape(512)              # hidden slot -> hidden unit
-        head = torch.zeros(32, 512, device=dev)
-        head[:self.shape.n_action] = q.advantage.weight.detach().float()
-        head[self.shape.n_action] = q.value.weight.detach().float()[0]
+        head, _ = _head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], dev)
         t = {
             "conv1": fragment_order(w1), "conv2": fragment_order(w2), "dense_view": fragment_order(wv),
             "dense_emb": fragment_order(we), "head": fragment_order(head[:, hidden]),
@@ -120,10 +167,9 @@ class HipDqnPolicy(_Packed):
             "dense_emb_bias": q.dense_emb.bias.detach().float()[hidden[:256]].contiguous(),
         }
         w = _Weights()
-        for k, v in t.items():
-            setattr(w, k, v.data_ptr())
+        _set_pointers(w, t)
         w.value_bias = float(q.value.bias.detach().float().item())
-        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False       # (the tensors stay alive as long as the pointers are in use)
+        self._set_packed(t, w, stamp)
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -138,18 +184,11 @@ class HipDqnPolicy(_Packed):
         n = view.shape[0]
         actions = torch.empty(n, dtype=torch.int32, device=view.device)
         q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=view.device) if want_q else None
-        nbytes = ctypes.c_size_t(0)
-        self._lib.policy_dqn_act_bytes(ctypes.byref(self.shape), min(n, self.chunk), ctypes.byref(nbytes))
-        need = nbytes.value          # (activations in the kernels' own layout + the conv kernel's dump line)
-        if self._work is None or self._work.numel() < need:
-            self._work = torch.empty(need, dtype=torch.uint8, device=view.device)
-        stream = torch.cuda.current_stream(view.device).cuda_stream
-        for beg in range(0, n, self.chunk):
-            m = min(self.chunk, n - beg)
-            rc = call(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
-                                            self._work.data_ptr(), actions[beg:].data_ptr(), q[beg:].data_ptr() if want_q else None, stream)
-            if rc != 0:
-                raise RuntimeError("policy_dqn_infer failed (%d)" % rc)
+        self._grow_work(view.device, self._lib.policy_dqn_act_bytes, min(n, self.chunk))       # (activations in the kernels' own layout + the conv kernel's dump line)
+        stream = _stream(view.device)
+        self._chunked("policy_dqn_infer", n, self.chunk, lambda beg, m: call(
+            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, self._work.data_ptr(),
+            actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
         return (actions, q) if want_q else actions
 
 
@@ -186,30 +225,21 @@ class HipDqnPolicyF32(_Packed):
     network's own arithmetic -- computed by k_dqn_conv_f32 + k_dqn_head_f32 on v_mfma_f32_32x32x2_f32 (magent_amd/csrc/policy_f32.hip)"""
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072):
-        self._lib = c_lib.load()
-        self.qnet, self.device, self.chunk = qnet, torch.device(device), int(chunk)
-        h, w, c = view_space
-        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        super().__init__(qnet, view_space, feature_space, n_action, device, chunk)
         if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 policy kernels")
-        self.k_dense = (h - 4) * (w - 4) * 32
-        self._packed, self._work, self._stamp = None, None, None
-        self.dirty = True      # (set by a caller: repack whatever the stamp says)
+        self.k_dense = (view_space[0] - 4) * (view_space[1] - 4) * 32
 
     @torch.no_grad()
     def pack(self):
         q, dev = self.qnet, self.device
         stamp = _SourceStamp(q)
         t = _trunk_f32(q, self.shape, dev)
-        head = torch.zeros(32, 512, device=dev)
-        head[:self.shape.n_action] = q.advantage.weight.detach().float()
-        head[self.shape.n_action] = q.value.weight.detach().float()[0]
-        t["head"] = fragment_order_f32(head)
+        t["head"] = fragment_order_f32(_head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], dev)[0])
         w = _Weights()
-        for k, v in t.items():
-            setattr(w, k, v.data_ptr())
+        _set_pointers(w, t)
         w.value_bias = float(q.value.bias.detach().float().item())
-        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False
+        self._set_packed(t, w, stamp)
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -222,17 +252,11 @@ class HipDqnPolicyF32(_Packed):
         n = view.shape[0]
         actions = torch.empty(n, dtype=torch.int32, device=view.device)
         q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=view.device) if want_q else None
-        nbytes = ctypes.c_size_t(0)
-        self._lib.policy_dqn_f32_act_bytes(ctypes.byref(self.shape), min(n, self.chunk), ctypes.byref(nbytes))
-        if self._work is None or self._work.numel() < nbytes.value:
-            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=view.device)
-        stream = torch.cuda.current_stream(view.device).cuda_stream
-        for beg in range(0, n, self.chunk):
-            m = min(self.chunk, n - beg)
-            rc = self._lib.policy_dqn_infer_f32(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
-                                                self._work.data_ptr(), actions[beg:].data_ptr(), q[beg:].data_ptr() if want_q else None, stream)
-            if rc != 0:
-                raise RuntimeError("policy_dqn_infer_f32 failed (%d)" % rc)
+        self._grow_work(view.device, self._lib.policy_dqn_f32_act_bytes, min(n, self.chunk))
+        stream = _stream(view.device)
+        self._chunked("policy_dqn_infer_f32", n, self.chunk, lambda beg, m: self._lib.policy_dqn_infer_f32(
+            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, self._work.data_ptr(),
+            actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
         return (actions, q) if want_q else actions
 
 
@@ -248,19 +272,13 @@ class HipDrqnPolicyF32(_Packed):
 
     The state table is the last call's output: its ids in call order, their states (row k: the k-th id's), and for the next call's lookup
     the ids sorted stably with their rows.  An id of the next call takes the state of its last occurrence in the table, any other id
-    starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  `lib`: a library other than the
-    product's (the tests' emulated build; its "device" memory is the host's, so the tensors are CPU tensors)."""
+    starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  `lib`: _Packed."""
     STATE = 512
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072, lib=None):
-        self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
-        self.qnet, self.device, self.chunk = qnet, torch.device(device), int(chunk)
-        h, w, c = view_space
-        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        super().__init__(qnet, view_space, feature_space, n_action, device, chunk, lib)
         if qnet.rnn.hidden_size != self.STATE or not self._lib.policy_drqn_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 DRQN kernels")
-        self._packed, self._work, self._stamp = None, None, None
-        self.dirty = True      # (set by a caller: repack whatever the stamp says)
         self.clear()
 
     # ---- the state table
@@ -303,22 +321,16 @@ class HipDrqnPolicyF32(_Packed):
         # a zero state: W_h 0 is 0, or NaN where a row of W_h is not finite (torch's W_h @ 0)
         w0 = torch.where(torch.isfinite(whh).all(dim=1), torch.zeros_like(bhh), torch.full_like(bhh, float("nan")))
         t["gru_bias0"] = bias(bhh + w0)
-        head, hb = torch.zeros(32, S, device=dev), torch.zeros(32, device=dev)
         if q.use_dueling:
-            head[:A] = q.advantage.weight.detach().float()
-            head[A] = q.value.weight.detach().float()[0]
-            hb[A] = q.value.bias.detach().float()[0]
+            head, hb = _head_32x512([(0, q.advantage.weight), (A, q.value.weight)], dev, [(A, q.value.bias)])
         else:
-            head[:A] = q.value.weight.detach().float()
-            hb[:A] = q.value.bias.detach().float()
+            head, hb = _head_32x512([(0, q.value.weight)], dev, [(0, q.value.bias)])
         t["head"], t["head_bias"] = fragment_order_f32(head), hb
         w = _DrqnWeights()
-        for k in ("conv1", "conv2", "dense_view", "dense_emb", "conv2_bias", "dense_view_bias", "dense_emb_bias"):
-            setattr(w.trunk, k, t[k].data_ptr())
-        for k in ("gru", "gru_bias", "gru_bias0", "head", "head_bias"):
-            setattr(w, k, t[k].data_ptr())
+        _set_pointers(w.trunk, t, ("conv1", "conv2", "dense_view", "dense_emb", "conv2_bias", "dense_view_bias", "dense_emb_bias"))
+        _set_pointers(w, t, ("gru", "gru_bias", "gru_bias0", "head", "head_bias"))
         w.dueling = int(bool(q.use_dueling))
-        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False
+        self._set_packed(t, w, stamp)
 
     # ---- one step
     @torch.no_grad()
@@ -335,20 +347,14 @@ class HipDrqnPolicyF32(_Packed):
         actions = torch.empty(n, dtype=torch.int32, device=dev)
         q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=dev) if want_q else None
         new_states = torch.empty((n, self.STATE), dtype=torch.float32, device=dev)
-        nbytes = ctypes.c_size_t(0)
-        self._lib.policy_drqn_f32_workspace_bytes(ctypes.byref(self.shape), min(n, self.chunk), ctypes.byref(nbytes))
-        if self._work is None or self._work.numel() < nbytes.value:
-            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
+        self._grow_work(dev, self._lib.policy_drqn_f32_workspace_bytes, min(n, self.chunk))
+        stream = _stream(dev)
         count = int(self._sorted.numel())
         table = (self._sorted.data_ptr(), self._rows.data_ptr(), self._states.data_ptr()) if count else (None, None, None)
-        for beg in range(0, n, self.chunk):
-            m = min(self.chunk, n - beg)
-            rc = self._lib.policy_drqn_infer_f32(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
-                                                 ids[beg:].data_ptr(), table[0], table[1], table[2], count, new_states[beg:].data_ptr(),
-                                                 self._work.data_ptr(), actions[beg:].data_ptr(), q[beg:].data_ptr() if want_q else None, stream)
-            if rc != 0:
-                raise RuntimeError("policy_drqn_infer_f32 failed (%d)" % rc)
+        self._chunked("policy_drqn_infer_f32", n, self.chunk, lambda beg, m: self._lib.policy_drqn_infer_f32(
+            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, ids[beg:].data_ptr(),
+            table[0], table[1], table[2], count, new_states[beg:].data_ptr(), self._work.data_ptr(), actions[beg:].data_ptr(),
+            _ptr(q[beg:] if want_q else None), stream))
         self._set_table(ids, new_states)
         return (actions, q) if want_q else actions
 
@@ -368,21 +374,15 @@ class HipA2cPolicyF32(_Packed):
     The draw is the inverse CDF of one uniform number per agent (include/magent_policy.h: policy_a2c_infer_f32).  Without CommNet a call
     of n agents goes to the kernels `chunk` agents at a time (every agent's row is its own).  With CommNet the mean of the other agents
     spans the call, so the whole n goes to ONE C call whatever `chunk` is: the column sums are then taken over the same blocks of agents
-    in the same order, and the result does not depend on `chunk`.  `lib`: a library other than the product's (the tests' emulated build;
-    its "device" memory is the host's, so the tensors are CPU tensors)."""
+    in the same order, and the result does not depend on `chunk`.  `lib`: _Packed."""
 
     _source = "net"
 
     def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
-        self._lib = c_lib.declare_policy(lib) if lib is not None else c_lib.load()
-        self.net, self.device, self.chunk = net, torch.device(device), int(chunk)
-        h, w, c = view_space
-        self.shape = _Shape(h, w, c, feature_space[0], n_action)
+        super().__init__(net, view_space, feature_space, n_action, device, chunk, lib)
         self.use_comm = net.comm is not None
         if net.dense.in_features != 512 or net.dense.out_features != 512 or not self._lib.policy_a2c_f32_supported(ctypes.byref(self.shape)):
             raise ValueError("network shape not taken by the HIP f32 A2C kernels")
-        self._packed, self._work, self._stamp = None, None, None
-        self.dirty = True      # (set by a caller: repack whatever the stamp says)
 
     @torch.no_grad()
     def pack(self):
@@ -397,19 +397,16 @@ class HipA2cPolicyF32(_Packed):
             "dense_emb_bias": net.dense_emb.bias.detach().float().contiguous(),
             "dense_bias": net.dense.bias.detach().float().contiguous(),
         }
-        head, hb = torch.zeros(32, 512, device=dev), torch.zeros(32, device=dev)
-        head[:A], hb[:A] = net.policy.weight.detach().float(), net.policy.bias.detach().float()
-        head[A], hb[A] = net.value.weight.detach().float()[0], net.value.bias.detach().float()[0]
+        head, hb = _head_32x512([(0, net.policy.weight), (A, net.value.weight)], dev, [(0, net.policy.bias), (A, net.value.bias)])
         t["head"], t["head_bias"] = fragment_order_f32(head), hb
         w = _A2cWeights()
-        for k, v in t.items():
-            setattr(w, k, v.data_ptr())
+        _set_pointers(w, t)
         if self.use_comm:
             for s, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
                 t["comm%d" % s] = fragment_order_f32(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
                 w.comm[s] = t["comm%d" % s].data_ptr()
         w.use_comm = int(self.use_comm)
-        self._packed, self._w, self._stamp, self.dirty = t, w, stamp, False       # (the tensors stay alive as long as the pointers are in use)
+        self._set_packed(t, w, stamp)
 
     @torch.no_grad()
     def infer(self, view, feature, u=None, want_policy=False, want_value=False):
@@ -428,18 +425,12 @@ class HipA2cPolicyF32(_Packed):
         actions = torch.empty(n, dtype=torch.int32, device=dev)
         policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
         value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
-        chunk = n if self.use_comm else self.chunk
-        nbytes = ctypes.c_size_t(0)
-        self._lib.policy_a2c_f32_workspace_bytes(ctypes.byref(self.shape), min(n, chunk), int(self.use_comm), ctypes.byref(nbytes))
-        if self._work is None or self._work.numel() < nbytes.value:
-            self._work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else None
-        for beg in range(0, n, max(chunk, 1)):
-            m = min(chunk, n - beg)
-            rc = self._lib.policy_a2c_infer_f32(ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m,
-                                                u[beg:].data_ptr(), self._work.data_ptr(), actions[beg:].data_ptr(),
-                                                policy[beg:].data_ptr() if want_policy else None, value[beg:].data_ptr() if want_value else None, stream)
-            if rc != 0:
-                raise RuntimeError("policy_a2c_infer_f32 failed (%d)" % rc)
+        chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
+        self._grow_work(dev, self._lib.policy_a2c_f32_workspace_bytes, min(n, chunk), int(self.use_comm))
+        stream = _stream(dev)
+        self._chunked("policy_a2c_infer_f32", n, chunk, lambda beg, m: self._lib.policy_a2c_infer_f32(
+            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
+            self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
+            _ptr(value[beg:] if want_value else None), stream))
         out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
         return out if len(out) > 1 else actions

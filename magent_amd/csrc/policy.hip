@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/magent_policy.h"
+#include "policy_host.h"
 #include "tune.h"
 
 namespace {
@@ -589,28 +590,16 @@ static int dqn_infer(const PolicyDqnShape *s, const PolicyDqnWeights *w, const v
     if (lds > 150 * 1024) return 1;
     constexpr int conv_wpc = 2;      // workgroups of k_dqn_conv per CU (1 and 3 measured slower: profiles/r03_policy.txt)
     const bool f13 = H == 13 && W == 13;
-    // the stream's device is made current (launches and function attributes are per device), and the dynamic-LDS allowance is
-    // granted once per DEVICE, not once per process
-    // (the caller's current device is put back when the call returns: a C-ABI call must not leave a side effect in a multi-GPU process)
-    int dev = 0, caller_dev = -1;
-    if (hipGetDevice(&caller_dev) != hipSuccess) return 2;
-    if (st) { if (hipStreamGetDevice(st, &dev) != hipSuccess || hipSetDevice(dev) != hipSuccess) return 2; }
-    else dev = caller_dev;
-    struct Restore { int d, cur; ~Restore() { if (d != cur) (void)hipSetDevice(d); } } restore{caller_dev, dev};
-    constexpr int MAX_DEV = 64;
-    if (dev < 0 || dev >= MAX_DEV) return 2;
-    static bool lds_ok_dev[MAX_DEV] = {};
-    bool &lds_ok = lds_ok_dev[dev];
-    if (!lds_ok) {
-        const void *convs[5] = {reinterpret_cast<const void *>(k_dqn_conv<false, false>), reinterpret_cast<const void *>(k_dqn_conv<true, false>),
-                                reinterpret_cast<const void *>(k_dqn_conv<false, true>), reinterpret_cast<const void *>(k_dqn_conv<true, true>),
-                                reinterpret_cast<const void *>(k_dqn_conv<true, true, true>)};
-        for (const void *f : convs)
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
-        lds_ok = true;
-    }
+    // the stream's device is made current and the dynamic-LDS allowance granted once per device (policy_host.h)
+    magent_amd::StreamDevice on(st);
+    static magent_amd::LdsAllowance lds_ok;
+    if (!on.ok || !lds_ok.grant(on.dev, {{reinterpret_cast<const void *>(k_dqn_conv<false, false>), 150 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_conv<true, false>), 150 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_conv<false, true>), 150 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_conv<true, true>), 150 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_conv<true, true, true>), 150 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_head<false>), (int)HEAD_LDS},
+                                         {reinterpret_cast<const void *>(k_dqn_head<true>), (int)HEAD_LDS}})) return 2;
     ConvArgs C{};
     C.view = view; C.act = (__bf16 *)act_workspace; C.w1 = (const bf16x8 *)w->conv1; C.w2 = (const bf16x8 *)w->conv2; C.b2 = w->conv2_bias;
     C.n = n; C.H = H; C.W = W; C.C = s->view_c; C.VP = VP; C.AP = AP; C.n_tiles = (n + CONV_TA - 1) / CONV_TA; C.dump = (bf16x8 *)((char *)act_workspace + act_bytes(s, n));

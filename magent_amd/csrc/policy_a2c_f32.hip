@@ -12,19 +12,21 @@
 // 8 q + 4 g + 0..3 of its 32-wide tile, natural order.  Every result column (agent) of an MFMA depends on that agent's operands alone, so
 // an agent's row does not depend on where in a tile, a workgroup or a launch it sits.
 //
-// k_a2c_trunk_f32 : the two input layers as k_dqn_head_f32 does its dense layer -- 128 agents per workgroup of 8 waves, wave w owns output
-//   tile w for all four agent tiles (one weight float4 from L2 and four activation float4 from LDS feed 16 MFMAs).  The view rows are K =
+// k_a2c_trunk_f32 : the two input layers by the loops k_dqn_head_f32 does its dense layer with (policy_f32_dev.h: dense_main,
+//   stage_features, dense_emb, hidden_out) -- 128 agents per workgroup of 8 waves, wave w owns output tile w for all four agent tiles (one
+//   weight float4 from L2 and four activation float4 from LDS feed 16 MFMAs); this kernel supplies the chunk stager.  The view rows are K =
 //   H W C floats, 4-byte aligned only (battle: 1183), so a K-chunk of 64 values per agent goes through registers into LDS by 4-byte
 //   loads -- a wave reads 64 consecutive floats of one row -- double buffered; values past K are zeros (K is padded to a multiple of 8 with
 //   zero weights), rows past n repeat row n - 1 and are not stored.  x = [xv | xe] goes to HBM as float[n][512].
 // k_a2c_layer_f32 : a [n] x [512] layer over K = 512 (<false>: h = relu(x Wd^T + bd)) or K = 1024 (<true>: one CommNet step as ONE GEMM,
 //   [others | h] against [C_s | H_s] side by side; others is formed from the h row and the column sums as the operand is fed, tanh in
 //   registers).  A wave owns 32 agents x 4 output tiles (four accumulators: per group of 8 K-values one activation float4 and four weight
-//   float4 feed 16 MFMAs), operands of the next two groups load while the current two's 32 MFMAs run; as k_drqn_gru_f32, from L2 / HBM.
+//   float4 feed 16 MFMAs), operands of the next two groups load while the current two's 32 MFMAs run (policy_f32_dev.h: pingpong, the
+//   driver k_drqn_gru_f32 uses), from L2 / HBM.
 // k_a2c_colsum_part_f32 + k_a2c_colsum_f32 : the CommNet column sums without float atomics -- partial sums over blocks of 256 agents (block
 //   b: agents 256 b .. 256 b + 255 of the call, added in agent order), then the blocks added in block order.  The sums are a function of
 //   the call's inputs alone.
-// k_a2c_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 (outputs 0..A-1 the policy's, output A the value's), softmax with the
+// k_a2c_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 (head_gemm512; outputs 0..A-1 the policy's, output A the value's), softmax with the
 //   row maximum subtracted, clamp, and the draw by the lane that holds the agent's action 0 (the row goes through LDS: a lane pair holds it).
 //
 // NaN contract: relu is IEEE maximum, tanhf and expf keep a NaN, the clamp is two comparisons (a NaN fails both and stays);
@@ -37,18 +39,15 @@
 
 #include "../../include/magent_policy.h"
 #include "policy_f32_dev.h"
+#include "policy_host.h"
 
 namespace {
 
-using magent_amd::f32::f32x16;
-using magent_amd::f32::f32x4;
-using magent_amd::f32::mfma4;
-using magent_amd::f32::relu;
+using namespace magent_amd::f32;      // the vector types, mfma4, relu, and the shared blocks: the dense pair, pingpong, head_gemm512, out_of
 
 constexpr int HID = 512;
 // ---------------------------------------------------------------------------------------------------- the input layers
-constexpr int TR_THREADS = 512, TR_M = 128, TR_KC = 64;            // 128 agents per workgroup of 8 waves; K staged 64 values at a time
-constexpr int TR_ABUF = TR_M * (TR_KC / 4);                          // float4 units of one activation buffer: 32 KB
+constexpr int TR_THREADS = DENSE_THREADS, TR_M = DENSE_M, TR_KC = DENSE_KC, TR_ABUF = DENSE_ABUF;      // the shared dense pair's workgroup (policy_f32_dev.h)
 constexpr int TR_FMAX = 64;                                          // most features (padded to 8)
 constexpr int TR_KMAX = 4096;                                        // most view values: the packed dense_view (K x 256 floats) stays inside one 4 MB L2
 constexpr size_t TR_LDS = ((size_t)2 * TR_ABUF + (size_t)TR_M * (TR_FMAX / 4)) * 16;      // two activation buffers + the features: 96 KB
@@ -63,22 +62,13 @@ struct TrunkArgs {
     float *x;                 // [n][512] relu(dense_view) || relu(dense_emb)
 };
 
-// rows of 16 float4, the unit index xor-ed with the row's low bits (policy_f32.hip: act_slot)
-__device__ __forceinline__ int act_slot(int row, int unit) { return row * 16 + (unit ^ (row & 15)); }
-
 __global__ void __launch_bounds__(TR_THREADS) k_a2c_trunk_f32(TrunkArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     f32x4 *s_act = (f32x4 *)s_raw;                         // [2][128 agents][16 units], swizzled
     float *s_feat = (float *)(s_act + 2 * TR_ABUF);        // [128 agents][FK]
-    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6;
     const int a0 = blockIdx.x * TR_M;
-    const int n_groups = A.KG, total = (n_groups + 7) / 8;
-    const f32x4 *wbase = A.wv + (size_t)w * 64 + l;        // fragment (group m, tile w) = wbase[m * 8 * 64]
-
-    for (int k = tid; k < TR_M * A.FK; k += TR_THREADS) {
-        const int row = k / A.FK, f = k - row * A.FK;
-        s_feat[k] = (f < A.F && a0 + row < A.n) ? A.feat[(size_t)(a0 + row) * A.F + f] : 0.0f;
-    }
+    stage_features(s_feat, A.feat, a0, A.n, A.F, A.FK);
     // staging: wave w moves value l of the chunk for rows w, w + 8, .. w + 120 (64 consecutive floats of a row per load)
     float ar[16];
     auto aload = [&](int c) {
@@ -93,71 +83,11 @@ __global__ void __launch_bounds__(TR_THREADS) k_a2c_trunk_f32(TrunkArgs A) {
 #pragma unroll
         for (int i = 0; i < 16; i++) ((float *)(s_act + buf * TR_ABUF + act_slot(w + 8 * i, l >> 2)))[l & 3] = ar[i];
     };
-    f32x4 wr[2][8];          // the wave's weight fragments: this chunk's and the next one's
-    auto wload = [&](int c, f32x4 (&dst)[8]) {
-#pragma unroll
-        for (int m = 0; m < 8; m++) dst[m] = wbase[(size_t)min(c * 8 + m, n_groups - 1) * 8 * 64];
-    };
     f32x16 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
-
-    aload(0);
-    wload(0, wr[0]);
-    astore(0);
-    if (total > 1) aload(1);
-    __syncthreads();
-    auto chunk = [&](int c, f32x4 (&wc)[8], f32x4 (&wn)[8]) __attribute__((always_inline)) {
-        const int buf = c & 1;
-        const int groups = min(8, n_groups - c * 8);
-        if (c + 1 < total) wload(c + 1, wn);
-        f32x4 x[2][4];
-        auto xread = [&](int m, f32x4 (&dst)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) dst[j] = s_act[buf * TR_ABUF + act_slot(32 * j + r32, 2 * m + g)];
-        };
-        xread(0, x[0]);
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            if (m < 7) xread(m + 1, x[(m + 1) & 1]);
-            if (m < groups) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = mfma4(wc[m], x[m & 1][j], acc[j]);
-            }
-            if (m == 1 && c + 1 < total) astore(buf ^ 1);    // the next chunk (its buffer was last read two barriers back)
-        }
-        if (c + 2 < total) aload(c + 2);
-        __syncthreads();
-    };
-    for (int c = 0; c < total; c += 2) {
-        chunk(c, wr[0], wr[1]);
-        if (c + 1 < total) chunk(c + 1, wr[1], wr[0]);
-    }
-    // relu(acc + bias) -> one half of x: lane (agent, g) of output tile w holds units 32 w + 8 q + 4 g + 0..3
-    auto hidden_out = [&](const float *bias, int half) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
-                if (a0 + 32 * j + r32 < A.n) *(f32x4 *)(A.x + (size_t)(a0 + 32 * j + r32) * HID + 256 * half + 32 * w + 8 * q + 4 * g) = v;
-            }
-        }
-    };
-    hidden_out(A.bv, 0);
-    // the feature embedding: K = FK (output tile w, four agent tiles)
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
-    for (int m = 0; m < A.FK / 8; m++) {
-        const f32x4 we = A.we[((size_t)m * 8 + w) * 64 + l];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const f32x4 x = *(const f32x4 *)(s_feat + (32 * j + r32) * A.FK + 8 * m + 4 * g);
-            acc[j] = mfma4(we, x, acc[j]);
-        }
-    }
-    hidden_out(A.be, 1);
+    dense_main(acc, s_act, A.wv, A.KG, aload, astore);
+    hidden_out(acc, A.bv, ToX{A.x, a0, A.n, 0});
+    dense_emb(acc, s_feat, A.we, A.FK);
+    hidden_out(acc, A.be, ToX{A.x, a0, A.n, 1});
 }
 
 // ---------------------------------------------------------------------------------------------------- dense 512 and the CommNet step
@@ -211,14 +141,7 @@ __global__ void __launch_bounds__(LY_THREADS) k_a2c_layer_f32(LayerArgs A) {
                 for (int t = 0; t < LY_TILES; t++) acc[t] = mfma4(d[j][2 + t], x, acc[t]);
             }
         };
-        constexpr int NC = 64 / LY_CHUNK;
-        load(0, op[0]);
-        for (int c = 0; c < NC; c += 2) {
-            load(c + 1, op[1]);
-            run(op[0]);
-            if (c + 2 < NC) load(c + 2, op[0]);
-            run(op[1]);
-        }
+        pingpong<64 / LY_CHUNK>(op, load, run);
     };
     if (COMM) phase(std::integral_constant<bool, true>{});
     phase(std::integral_constant<bool, false>{});
@@ -277,29 +200,21 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
     const int tile0 = (blockIdx.x * PH_WAVES + w) * 32;
     const int agent = min(tile0 + r32, A.n - 1);                 // (waves past n repeat the last agent and store nothing)
     const bool live = tile0 + r32 < A.n;
-    const f32x4 *hp = (const f32x4 *)(A.h + (size_t)agent * HID) + g;
-    f32x16 acc = {0};
-    f32x4 hw[2], hx[2];
-    hw[0] = A.wh[l];
-    hx[0] = hp[0];
-    for (int m = 0; m < HID / 8; m++) {
-        if (m + 1 < HID / 8) { hw[(m + 1) & 1] = A.wh[(m + 1) * 64 + l]; hx[(m + 1) & 1] = hp[2 * (m + 1)]; }
-        acc = mfma4(hw[m & 1], hx[m & 1], acc);
-    }
-    // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen
+    f32x16 acc = head_gemm512(A.wh, l, (const f32x4 *)(A.h + (size_t)agent * HID) + g);
+    // lane (agent, g) holds outputs out_of(r, g); its partner lane ^ 32 the other sixteen
 #pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] += A.bh[(r & 3) + 8 * (r >> 2) + 4 * g];
+    for (int r = 0; r < 16; r++) acc[r] += A.bh[out_of(r, g)];
     float top = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        const int o = out_of(r, g);
         if (o < A.n_action) top = fmaxf(top, acc[r]);            // (a NaN is passed over here and reaches the sum through its own exp)
     }
     top = fmaxf(top, __shfl_xor(top, 32));
     float e[16], sum = 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        const int o = out_of(r, g);
         e[r] = o < A.n_action ? expf(acc[r] - top) : 0.0f;
         sum += e[r];
     }
@@ -307,7 +222,7 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
     float *row = s_p + (w * 32 + r32) * PH_PITCH;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
+        const int o = out_of(r, g);
         float p = e[r] / sum;
         p = p < 1e-10f ? 1e-10f : (p > (float)(1.0 - 1e-10) ? (float)(1.0 - 1e-10) : p);      // torch.clamp: a NaN stays
         if (o < A.n_action) {
@@ -371,18 +286,9 @@ int policy_a2c_infer_f32(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, 
     if (!view || !feat || !u || !actions || !workspace) return 1;
     if ((uintptr_t)workspace & 15) return 1;                     // (rows are read and written as float4)
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0, caller_dev = -1;
-    if (hipGetDevice(&caller_dev) != hipSuccess) return 2;
-    if (st) { if (hipStreamGetDevice(st, &dev) != hipSuccess || hipSetDevice(dev) != hipSuccess) return 2; }
-    else dev = caller_dev;
-    struct Restore { int d, cur; ~Restore() { if (d != cur) (void)hipSetDevice(d); } } restore{caller_dev, dev};
-    constexpr int MAX_DEV = 64;
-    if (dev < 0 || dev >= MAX_DEV) return 2;
-    static bool lds_ok_dev[MAX_DEV] = {};
-    if (!lds_ok_dev[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_a2c_trunk_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TR_LDS) != hipSuccess) return 2;
-        lds_ok_dev[dev] = true;
-    }
+    magent_amd::StreamDevice on(st);
+    static magent_amd::LdsAllowance lds_ok;
+    if (!on.ok || !lds_ok.grant(on.dev, {{reinterpret_cast<const void *>(k_a2c_trunk_f32), (int)TR_LDS}})) return 2;
     const Layout L = layout(n, comm);
     char *ws = (char *)workspace;
     float *x = (float *)(ws + L.x), *h0 = (float *)(ws + L.h0);

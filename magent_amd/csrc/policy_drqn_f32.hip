@@ -17,14 +17,15 @@
 //   four accumulators: r and z over all of K, n_x over x, n_h over h (r multiplies n_h alone) -- 64 VGPRs.  The packed weights put the
 //   three gate tiles of a hidden tile side by side ([K / 8][16 tiles][3 gates][64 lanes]): per group of 8 K-values a lane loads its
 //   activation float4 and three weight float4, which feed 12 MFMAs (768 cycles); operands of the next four groups load while the
-//   current four's 48 MFMAs run.  A workgroup is 8 waves = 256 agents on ONE hidden tile, so its waves read the same weights (L1/L2) and
+//   current four's 48 MFMAs run (policy_f32_dev.h: pingpong, shared with k_a2c_layer_f32).  A workgroup is 8 waves = 256 agents on ONE hidden tile, so its waves read the same weights (L1/L2) and
 //   the x rows of an agent group are read by the 16 hidden tiles' workgroups (L2).  The gates are applied in registers and h' goes
 //   straight to the new state table.
 //   The previous state of an agent is the row of the previous call whose id is the LAST equal entry of that call's ids sorted stably
 //   (binary search: duplicates -- the dict's last occurrence); an id not found starts from zeros.  With an empty table the <false>
 //   variant skips the h half and takes the biases of a zero state (W_h 0 + b_h, which the host computes: NaN where W_h holds a
 //   non-finite weight, as torch's W_h @ 0).
-// k_drqn_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 state units, then the dueling combination and torch.argmax's order.
+// k_drqn_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 state units (policy_f32_dev.h: head_gemm512, shared with
+//   k_a2c_head_f32), then the dueling combination and torch.argmax's order (q_epilogue, shared with k_dqn_head_f32).
 //
 // NaN contract: nothing launders a NaN -- sigmoid is 1 / (1 + exp(-v)), tanhf, relu is IEEE maximum; a NaN anywhere in an
 // agent's inputs or state reaches its Q row and its new state, and its action is the first NaN of that row, as the PyTorch path's argmax.
@@ -35,13 +36,11 @@
 
 #include "../../include/magent_policy.h"
 #include "policy_f32_dev.h"
+#include "policy_host.h"
 
 namespace {
 
-using magent_amd::f32::f32x16;
-using magent_amd::f32::f32x4;
-using magent_amd::f32::mfma4;
-using magent_amd::f32::q_before;
+using namespace magent_amd::f32;      // the vector types, mfma4, and the shared blocks: pingpong, head_gemm512, q_epilogue
 
 constexpr int STATE = 512, GRU_TILES = STATE / 32;
 constexpr int GRU_WAVES = 8, GRU_THREADS = 64 * GRU_WAVES, GRU_CHUNK = 4;     // groups of 8 K-values a wave has in flight per buffer
@@ -108,14 +107,7 @@ __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_f32(GruArgs A) {
                 else anx = mfma4(d[j][3], d[j][0], anx);
             }
         };
-        constexpr int NC = 64 / GRU_CHUNK;
-        load(0, op[0]);
-        for (int c = 0; c < NC; c += 2) {
-            load(c + 1, op[1]);
-            run(op[0]);
-            if (c + 2 < NC) load(c + 2, op[0]);
-            run(op[1]);
-        }
+        pingpong<64 / GRU_CHUNK>(op, load, run);
     };
     phase(std::integral_constant<bool, false>{});
     if (HAS_H) phase(std::integral_constant<bool, true>{});
@@ -156,48 +148,12 @@ __global__ void __launch_bounds__(QH_THREADS) k_drqn_head_f32(QHeadArgs A) {
     const int tile0 = (blockIdx.x * QH_WAVES + w) * 32;
     if (tile0 >= A.n) return;
     const int agent = min(tile0 + r32, A.n - 1);
-    const f32x4 *hp = (const f32x4 *)(A.h + (size_t)agent * STATE) + g;
-    f32x16 acc = {0};
-    f32x4 hw[2], hx[2];
-    hw[0] = A.wh[l];
-    hx[0] = hp[0];
-    for (int m = 0; m < STATE / 8; m++) {
-        if (m + 1 < STATE / 8) { hw[(m + 1) & 1] = A.wh[(m + 1) * 64 + l]; hx[(m + 1) & 1] = hp[2 * (m + 1)]; }
-        acc = mfma4(hw[m & 1], hx[m & 1], acc);
-    }
-    // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen (policy_f32.hip: k_dqn_head_f32)
+    f32x16 acc = head_gemm512(A.wh, l, (const f32x4 *)(A.h + (size_t)agent * STATE) + g);
 #pragma unroll
-    for (int r = 0; r < 16; r++) acc[r] += A.bh[(r & 3) + 8 * (r >> 2) + 4 * g];
-    float shift = 0.0f;
-    if (A.dueling) {
-        float sum = 0.0f, value = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
-            if (o < A.n_action) sum += acc[r];
-            if (o == A.n_action) value = acc[r];
-        }
-        sum += __shfl_xor(sum, 32);
-        value += __shfl_xor(value, 32);
-        shift = value - sum / (float)A.n_action;
-    }
-    float best = -INFINITY;
-    int arg = A.n_action;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
-        if (o < A.n_action && q_before(acc[r] + shift, o, best, arg)) { best = acc[r] + shift; arg = o; }
-    }
-    const float obest = __shfl_xor(best, 32);
-    const int oarg = __shfl_xor(arg, 32);
-    if (q_before(obest, oarg, best, arg)) { best = obest; arg = oarg; }
-    if (tile0 + r32 < A.n) {
-        if (g == 0) A.actions[agent] = arg;
-        if (A.q) {
-#pragma unroll
-            for (int r = 0; r < 16; r++) { const int o = (r & 3) + 8 * (r >> 2) + 4 * g; if (o < A.n_action) A.q[(size_t)agent * A.n_action + o] = acc[r] + shift; }
-        }
-    }
+    for (int r = 0; r < 16; r++) acc[r] += A.bh[out_of(r, g)];
+    // Q = acc + value - mean(advantage) (dueling) or acc, the argmax and the stores: q_epilogue
+    q_epilogue(acc, g, A.n_action, A.dueling != 0, [&](float value, float sum) { return value - sum / (float)A.n_action; },
+               tile0 + r32 < A.n, agent, A.actions, A.q);
 }
 
 static size_t x_offset(const PolicyDqnShape *s, int n) {       // the trunk's workspace, then x
@@ -229,11 +185,8 @@ int policy_drqn_infer_f32(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w
     int rc = magent_amd::f32::dqn_f32_trunk(s, &w->trunk, view, feat, n, workspace, x, stream);
     if (rc != 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0, caller_dev = -1;
-    if (hipGetDevice(&caller_dev) != hipSuccess) return 2;
-    if (st) { if (hipStreamGetDevice(st, &dev) != hipSuccess || hipSetDevice(dev) != hipSuccess) return 2; }
-    else dev = caller_dev;
-    struct Restore { int d, cur; ~Restore() { if (d != cur) (void)hipSetDevice(d); } } restore{caller_dev, dev};
+    magent_amd::StreamDevice on(st);
+    if (!on.ok) return 2;
     GruArgs G{};
     G.x = x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.count = count; G.n = n;
     G.w = (const f32x4 *)w->gru; G.bias = count > 0 ? w->gru_bias : w->gru_bias0; G.out = new_states;

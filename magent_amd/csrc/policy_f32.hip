@@ -33,22 +33,21 @@
 //   pitches == 4 (mod 16) sixteen-byte units every 16-lane group of a ds_read_b128 covers all 16 LDS columns, a tap is a constant offset.
 // k_dqn_head_f32 : dense K -> 256 as a GEMM over 128 agents per workgroup of 8 waves (wave w owns outputs 32 w .. 32 w + 31 for all four
 //   agent tiles: per group of 8 K-values ONE weight float4 from L2 and four activation float4 from LDS feed 16 MFMAs), activations double
-//   buffered through LDS a 64-value chunk at a time, the feature embedding, the dueling head and the argmax, fused.
+//   buffered through LDS a 64-value chunk at a time, the feature embedding, the dueling head and the argmax, fused.  The dense pair's
+//   loops are policy_f32_dev.h's (dense_main, stage_features, dense_emb, hidden_out), shared with k_a2c_trunk_f32: this kernel supplies
+//   how a chunk of the act_at workspace reaches LDS (aload / astore) and where the hidden halves go; the Q row and the argmax are
+//   q_epilogue, shared with k_drqn_head_f32.  The launcher's device selection and LDS allowance: policy_host.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/magent_policy.h"
 #include "policy_f32_dev.h"
+#include "policy_host.h"
 #include "tune.h"
 
 namespace {
 
-using magent_amd::f32::f32x16;
-using magent_amd::f32::f32x4;
-using magent_amd::f32::mfma4;
-using magent_amd::f32::q_before;
-using magent_amd::f32::relu;
-using magent_amd::f32::relu4;
+using namespace magent_amd::f32;      // the vector types, mfma4, relu4, and the shared blocks: out_of, the dense pair, q_epilogue
 
 // conv2's output, dense_view's input: [group of 128 agents][K-chunk of 64 values = two positions][agent][64 values] (as policy.hip's
 // act_at, in floats): one k_dqn_head_f32 workgroup reads one contiguous 32 KB block per K-chunk
@@ -166,7 +165,7 @@ __global__ void __launch_bounds__(CONV_THREADS) k_dqn_conv_f32(ConvArgs A) {
             const f32x4 *cb = s_c1 + g * PL1 + ag * AP + y * W + (q - y * W2);       // plane g (+ 2 m) of the top-left c1 position
             f32x16 acc;
 #pragma unroll
-            for (int r = 0; r < 16; r++) acc[r] = s_bias[(r & 3) + 8 * (r >> 2) + 4 * g];
+            for (int r = 0; r < 16; r++) acc[r] = s_bias[out_of(r, g)];
             f32x4 x[2][4];
             auto xread = [&](int tap, f32x4 (&dst)[4]) {
                 const int off = (tap / 3) * W + tap % 3;
@@ -189,8 +188,7 @@ __global__ void __launch_bounds__(CONV_THREADS) k_dqn_conv_f32(ConvArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------- dense + head
-constexpr int HEAD_THREADS = 512, HEAD_M = 128, HEAD_KC = 64;      // 128 agents per workgroup of 8 waves; K staged 64 values at a time
-constexpr int HEAD_ABUF = HEAD_M * (HEAD_KC / 4);                   // float4 units of one activation buffer: 128 agents x 16 = 32 KB
+constexpr int HEAD_THREADS = DENSE_THREADS, HEAD_M = DENSE_M, HEAD_ABUF = DENSE_ABUF;      // the shared dense pair's workgroup (policy_f32_dev.h)
 constexpr int HEAD_FMAX = 56;                                       // most features (padded to 8) the embedding's LDS image holds
 constexpr size_t HEAD_LDS = ((size_t)HEAD_M * 64 + (size_t)HEAD_M * (HEAD_FMAX / 4)) * 16;      // hidden half 128 KB (the loop's two 32 KB buffers lie inside) + features 28 KB
 
@@ -208,24 +206,17 @@ struct HeadArgs {
     float *x;                 // HIDDEN_OUT: [n][512] the hidden layer (the DRQN's GRU input); actions, q and wh are not used
 };
 
-// LDS images: rows of 16 float4 (activation chunk) / 64 float4 (hidden half), the unit index xor-ed with the row's low bits so that the 16
-// lanes of a ds_read_b128 service group (16 consecutive agents, one unit) cover all 16 columns
-__device__ __forceinline__ int act_slot(int row, int unit) { return row * 16 + (unit ^ (row & 15)); }
-__device__ __forceinline__ int hid_slot(int row, int unit) { return row * 64 + (unit ^ (row & 15)); }
-
 // HIDDEN_OUT (the DRQN's trunk, policy_f32_dev.h: dqn_f32_trunk): the hidden layer goes to A.x instead of through the dueling head
 template <bool HIDDEN_OUT>
 __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
     f32x4 *s_act = (f32x4 *)s_raw;                         // [2][128 agents][16 units], swizzled -- and, behind the main loop,
     f32x4 *s_hid = (f32x4 *)s_raw;                         // [128 agents][64 units]: one half of the hidden layer
-    f32x4 *s_feat = s_hid + HEAD_M * 64;                   // [128 agents][FK / 4 units]
+    float *s_feat = (float *)(s_hid + HEAD_M * 64);        // [128 agents][FK]
     const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
     const int a0 = blockIdx.x * HEAD_M;
     const int n_groups = A.K / 8;                          // groups of 8 K-values; 8 per chunk, the last chunk may be half (K is a multiple of 32)
-    const int total = (n_groups + 7) / 8;
-    const f32x4 *ablock = (const f32x4 *)A.act + (size_t)blockIdx.x * total * HEAD_ABUF;
-    const f32x4 *wbase = A.wv + (size_t)w * 64 + l;        // fragment (group m, tile w) = wbase[m * 8 * 64]
+    const f32x4 *ablock = (const f32x4 *)A.act + (size_t)blockIdx.x * ((n_groups + 7) / 8) * HEAD_ABUF;
 
     // staging: a chunk's block is 2048 float4 units (unit u: agent row u >> 4, piece u & 15); thread t moves units t + 512 i
     f32x4 ar[4];
@@ -241,67 +232,17 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
 #pragma unroll
         for (int i = 0; i < 4; i++) { const int u = tid + 512 * i; s_act[buf * HEAD_ABUF + act_slot(u >> 4, u & 15)] = ar[i]; }
     };
-    f32x4 wr[2][8];          // the wave's weight fragments: this chunk's and the next one's
-    auto wload = [&](int c, f32x4 (&dst)[8]) {
-#pragma unroll
-        for (int m = 0; m < 8; m++) dst[m] = wbase[(size_t)min(c * 8 + m, n_groups - 1) * 8 * 64];
-    };
     f32x16 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
-
-    aload(0);
-    wload(0, wr[0]);
-    astore(0);
-    if (total > 1) aload(1);
-    __syncthreads();
-    auto chunk = [&](int c, f32x4 (&wc)[8], f32x4 (&wn)[8]) __attribute__((always_inline)) {
-        const int buf = c & 1;
-        const int groups = min(8, n_groups - c * 8);
-        if (c + 1 < total) wload(c + 1, wn);                 // a chunk (16 x 8 MFMAs per wave) ahead of its use
-        f32x4 x[2][4];
-        auto xread = [&](int m, f32x4 (&dst)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) dst[j] = s_act[buf * HEAD_ABUF + act_slot(32 * j + r32, 2 * m + g)];
-        };
-        xread(0, x[0]);
-#pragma unroll
-        for (int m = 0; m < 8; m++) {
-            if (m < 7) xread(m + 1, x[(m + 1) & 1]);
-            if (m < groups) {
-#pragma unroll
-                for (int j = 0; j < 4; j++) acc[j] = mfma4(wc[m], x[m & 1][j], acc[j]);
-            }
-            if (m == 1 && c + 1 < total) astore(buf ^ 1);    // the next chunk, requested a chunk ago (its buffer was last read two barriers back)
-        }
-        if (c + 2 < total) aload(c + 2);
-        __syncthreads();
-    };
-    for (int c = 0; c < total; c += 2) {
-        chunk(c, wr[0], wr[1]);
-        if (c + 1 < total) chunk(c + 1, wr[1], wr[0]);
-    }
+    dense_main(acc, s_act, A.wv, n_groups, aload, astore);
     // ---- behind the main loop.  The features of the workgroup's agents go to LDS (FK / 8 groups of the embedding's reduction)
-    for (int k = tid; k < HEAD_M * A.FK; k += HEAD_THREADS) {
-        const int row = k / A.FK, f = k - row * A.FK;
-        ((float *)s_feat)[row * A.FK + f] = (f < A.F && a0 + row < A.n) ? A.feat[(size_t)(a0 + row) * A.F + f] : 0.0f;
+    stage_features(s_feat, A.feat, a0, A.n, A.F, A.FK);
+    if constexpr (HIDDEN_OUT) {
+        hidden_out(acc, A.bv, ToX{A.x, a0, A.n, 0});
+        __syncthreads();
+        dense_emb(acc, s_feat, A.we, A.FK);
+        hidden_out(acc, A.be, ToX{A.x, a0, A.n, 1});
+        return;
     }
-    // relu(acc + bias) -> one half of the hidden layer: lane (agent, g) of output tile w holds units 32 w + 8 q + 4 g + 0..3
-    auto hidden_out = [&](const float *bias, int half) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
-                if constexpr (HIDDEN_OUT) {
-                    if (a0 + 32 * j + r32 < A.n) *(f32x4 *)(A.x + (size_t)(a0 + 32 * j + r32) * 512 + 256 * half + 32 * w + 8 * q + 4 * g) = v;
-                } else {
-                    s_hid[hid_slot(32 * j + r32, 8 * w + 2 * q + g)] = v;
-                }
-            }
-        }
-    };
     // the dueling head: [32 outputs] x [128 agents], K = 512 hidden units in two halves; waves 0..3 take 32 agents each
     f32x16 h = {0};
     const int hagent = 32 * (w & 3) + r32;
@@ -315,60 +256,18 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head_f32(HeadArgs A) {
             }
         }
     };
-    hidden_out(A.bv, 0);       // (the main loop's last barrier is behind us: nobody reads the activation buffers any more)
+    hidden_out(acc, A.bv, ToHid{s_hid});       // (the main loop's last barrier is behind us: nobody reads the activation buffers any more)
     __syncthreads();
-    if constexpr (!HIDDEN_OUT) head_half(0);
-    // the feature embedding: K = FK, all eight waves (output tile w, four agent tiles)
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
-    for (int m = 0; m < A.FK / 8; m++) {
-        const f32x4 we = A.we[((size_t)m * 8 + w) * 64 + l];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const f32x4 x = *(const f32x4 *)((const float *)s_feat + (32 * j + r32) * A.FK + 8 * m + 4 * g);
-            acc[j] = mfma4(we, x, acc[j]);
-        }
-    }
-    if constexpr (HIDDEN_OUT) {
-        hidden_out(A.be, 1);
-        return;
-    }
+    head_half(0);
+    dense_emb(acc, s_feat, A.we, A.FK);
     __syncthreads();           // the first half of the head has read relu(dense_view)
-    hidden_out(A.be, 1);
+    hidden_out(acc, A.be, ToHid{s_hid});
     __syncthreads();
     head_half(1);
-    if (w < 4) {
-        // lane (agent, g) holds outputs (r & 3) + 8 (r >> 2) + 4 g; its partner lane ^ 32 the other sixteen.  The action is the argmax of the
-        // Q row itself, h + shift, in torch.argmax's order (q_before): a NaN anywhere in the network reaches the row, and then its first NaN
-        // is chosen, as the PyTorch path chooses it; every action lies in [0, n_action) whatever the input
-        float sum = 0.0f, value = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
-            if (o < A.n_action) sum += h[r];
-            if (o == A.n_action) value = h[r];
-        }
-        sum += __shfl_xor(sum, 32);
-        value += __shfl_xor(value, 32);
-        const float shift = value + A.value_bias - sum / (float)A.n_action;
-        float best = -INFINITY;
-        int arg = A.n_action;         // (not an action: every output of the row comes before it)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int o = (r & 3) + 8 * (r >> 2) + 4 * g;
-            if (o < A.n_action && q_before(h[r] + shift, o, best, arg)) { best = h[r] + shift; arg = o; }
-        }
-        const float obest = __shfl_xor(best, 32);
-        const int oarg = __shfl_xor(arg, 32);
-        if (q_before(obest, oarg, best, arg)) { best = obest; arg = oarg; }
-        if (a0 + hagent < A.n) {
-            if (g == 0) A.actions[a0 + hagent] = arg;
-            if (A.q) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) { const int o = (r & 3) + 8 * (r >> 2) + 4 * g; if (o < A.n_action) A.q[(size_t)(a0 + hagent) * A.n_action + o] = h[r] + shift; }
-            }
-        }
-    }
+    // Q = h + value + value_bias - mean(advantage), the argmax and the stores: q_epilogue
+    if (w < 4)
+        q_epilogue(h, g, A.n_action, true, [&](float value, float sum) { return value + A.value_bias - sum / (float)A.n_action; },
+                   a0 + hagent < A.n, a0 + hagent, A.actions, A.q);
 }
 
 static size_t act_bytes_f32(const PolicyDqnShape *s, int n) {      // whole groups of ACT_GROUP agents, whole K-chunks of 64
@@ -422,21 +321,12 @@ static int launch_f32(const PolicyDqnShape *s, const PolicyDqnWeightsF32 *w, con
     const int H = s->view_h, W = s->view_w, H2 = H - 4, W2 = W - 4;
     const int TA = conv_ta(s);
     const size_t lds = conv_lds(s, TA);
-    int dev = 0, caller_dev = -1;
-    if (hipGetDevice(&caller_dev) != hipSuccess) return 2;
-    if (st) { if (hipStreamGetDevice(st, &dev) != hipSuccess || hipSetDevice(dev) != hipSuccess) return 2; }
-    else dev = caller_dev;
-    struct Restore { int d, cur; ~Restore() { if (d != cur) (void)hipSetDevice(d); } } restore{caller_dev, dev};
-    constexpr int MAX_DEV = 64;
-    if (dev < 0 || dev >= MAX_DEV) return 2;
-    static bool lds_ok_dev[MAX_DEV] = {};
-    if (!lds_ok_dev[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_conv_f32<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_conv_f32<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head_f32<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_dqn_head_f32<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HEAD_LDS) != hipSuccess) return 2;
-        lds_ok_dev[dev] = true;
-    }
+    magent_amd::StreamDevice on(st);
+    static magent_amd::LdsAllowance lds_ok;
+    if (!on.ok || !lds_ok.grant(on.dev, {{reinterpret_cast<const void *>(k_dqn_conv_f32<4>), 160 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_conv_f32<2>), 160 * 1024},
+                                         {reinterpret_cast<const void *>(k_dqn_head_f32<false>), (int)HEAD_LDS},
+                                         {reinterpret_cast<const void *>(k_dqn_head_f32<true>), (int)HEAD_LDS}})) return 2;
     ConvArgs C{};
     C.view = view; C.act = (float *)act_workspace; C.w1 = (const f32x4 *)w->conv1; C.w2 = (const f32x4 *)w->conv2; C.b2 = w->conv2_bias;
     C.n = n; C.H = H; C.W = W; C.C = s->view_c; C.VP = pitch_for(H * W + 2, TA); C.AP = pitch_for((H - 2) * W, TA); C.n_tiles = (n + TA - 1) / TA;

@@ -1,7 +1,15 @@
 // policy_f32_dev.h -- what the float32 policy translation units share (internal; not part of the C-ABI):
 //   policy_f32.hip       the DQN: k_dqn_conv_f32 + k_dqn_head_f32, and the trunk launcher below
 //   policy_drqn_f32.hip  the DRQN: the DQN's trunk, then k_drqn_gru_f32 + k_drqn_head_f32
+//   policy_a2c_f32.hip   the A2C: k_a2c_trunk_f32, k_a2c_layer_f32 (+ the column sums), k_a2c_head_f32
 // Operand and fragment conventions: policy_f32.hip's header comment and include/magent_policy.h ("f32 fragment order").
+// The building blocks, each written once:
+//   out_of                                           which output a result register holds
+//   dense_main, stage_features, dense_emb,
+//   hidden_out with the sinks ToX / ToHid            the 128 agents x 256 outputs dense pair (k_dqn_head_f32, k_a2c_trunk_f32)
+//   head_gemm512                                     the one-wave K = 512, 32-output head GEMM (k_drqn_head_f32, k_a2c_head_f32)
+//   q_epilogue                                       the dueling combination, torch.argmax's pick, the stores (k_dqn_head_f32, k_drqn_head_f32)
+//   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -21,6 +29,8 @@ __device__ __forceinline__ f32x16 mfma4(const f32x4 &w, const f32x4 &x, f32x16 a
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(w[3], x[3], acc, 0, 0, 0);
     return acc;
 }
+// the output (of a 32-wide tile) that result register r of a lane of group g = lane >> 5 holds: a lane owns 8 q + 4 g + 0..3 for q = 0..3
+__device__ __forceinline__ int out_of(int r, int g) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
 // relu that keeps a NaN a NaN, as torch.relu does (fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0, and a poisoned view or a diverged network would
 // then act on finite garbage).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, the cost of the v_max_f32 it replaces; -0 gives +0.
 __device__ __forceinline__ float relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
@@ -31,6 +41,183 @@ __device__ __forceinline__ f32x4 relu4(const f32x16 &acc, int q) {
 // (v, o) come before (best, arg)?
 __device__ __forceinline__ bool q_before(float v, int o, float best, int arg) {
     return v != v ? (best == best || o < arg) : (best == best && (v > best || (v == best && o < arg)));
+}
+
+// ---------------------------------------------------------------------------------------------------- the 128 x 256 dense pair
+// dense K -> 256 as a GEMM over 128 agents per workgroup of 8 waves: wave w owns outputs 32 w .. 32 w + 31 for all four agent tiles (per
+// group of 8 K-values ONE weight float4 from L2 and four activation float4 from LDS feed 16 MFMAs), activations double buffered through
+// LDS a 64-value chunk at a time; then the feature embedding K = FK -> 256 from an LDS image of the features.  How a chunk reaches LDS,
+// when the features are staged, where the two halves of the hidden layer go and what lies between them is the calling kernel's.
+constexpr int DENSE_THREADS = 512, DENSE_M = 128, DENSE_KC = 64;      // 128 agents per workgroup of 8 waves; K staged 64 values at a time
+constexpr int DENSE_ABUF = DENSE_M * (DENSE_KC / 4);                  // float4 units of one activation buffer: 128 agents x 16 = 32 KB
+
+// LDS images: rows of 16 float4 (activation chunk) / 64 float4 (hidden half), the unit index xor-ed with the row's low bits so that the 16
+// lanes of a ds_read_b128 service group (16 consecutive agents, one unit) cover all 16 columns
+__device__ __forceinline__ int act_slot(int row, int unit) { return row * 16 + (unit ^ (row & 15)); }
+__device__ __forceinline__ int hid_slot(int row, int unit) { return row * 64 + (unit ^ (row & 15)); }
+
+// acc[j] (agent tile j, output tile w) = the dense layer over n_groups groups of 8 K-values (8 per chunk; the last chunk may be short).
+// s_act: [2][128 agents][16 units], swizzled (act_slot).  aload(c) requests chunk c into the caller's registers, astore(buf) puts the
+// requested chunk into s_act + buf * DENSE_ABUF; a chunk's weights are fetched a chunk ahead of their use.  Ends behind a barrier:
+// nobody reads the activation buffers any more.
+template <class ALoad, class AStore>
+__device__ __forceinline__ void dense_main(f32x16 (&acc)[4], const f32x4 *s_act, const f32x4 *wv, int n_groups, const ALoad &aload, const AStore &astore) {
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
+    const int total = (n_groups + 7) / 8;
+    const f32x4 *wbase = wv + (size_t)w * 64 + l;          // fragment (group m, tile w) = wbase[m * 8 * 64]
+    f32x4 wr[2][8];          // the wave's weight fragments: this chunk's and the next one's
+    auto wload = [&](int c, f32x4 (&dst)[8]) {
+#pragma unroll
+        for (int m = 0; m < 8; m++) dst[m] = wbase[(size_t)min(c * 8 + m, n_groups - 1) * 8 * 64];
+    };
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
+
+    aload(0);
+    wload(0, wr[0]);
+    astore(0);
+    if (total > 1) aload(1);
+    __syncthreads();
+    auto chunk = [&](int c, f32x4 (&wc)[8], f32x4 (&wn)[8]) __attribute__((always_inline)) {
+        const int buf = c & 1;
+        const int groups = min(8, n_groups - c * 8);
+        if (c + 1 < total) wload(c + 1, wn);                 // a chunk (16 x 8 MFMAs per wave) ahead of its use
+        f32x4 x[2][4];
+        auto xread = [&](int m, f32x4 (&dst)[4]) {
+#pragma unroll
+            for (int j = 0; j < 4; j++) dst[j] = s_act[buf * DENSE_ABUF + act_slot(32 * j + r32, 2 * m + g)];
+        };
+        xread(0, x[0]);
+#pragma unroll
+        for (int m = 0; m < 8; m++) {
+            if (m < 7) xread(m + 1, x[(m + 1) & 1]);
+            if (m < groups) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) acc[j] = mfma4(wc[m], x[m & 1][j], acc[j]);
+            }
+            if (m == 1 && c + 1 < total) astore(buf ^ 1);    // the next chunk, requested a chunk ago (its buffer was last read two barriers back)
+        }
+        if (c + 2 < total) aload(c + 2);
+        __syncthreads();
+    };
+    for (int c = 0; c < total; c += 2) {
+        chunk(c, wr[0], wr[1]);
+        if (c + 1 < total) chunk(c + 1, wr[1], wr[0]);
+    }
+}
+// the features of the workgroup's agents a0 .. a0 + 127 to LDS as [128 agents][FK] (FK: F padded to 8 with zeros; rows past n are zeros)
+__device__ __forceinline__ void stage_features(float *s_feat, const float *feat, int a0, int n, int F, int FK) {
+    const int tid = threadIdx.x;
+    for (int k = tid; k < DENSE_M * FK; k += DENSE_THREADS) {
+        const int row = k / FK, f = k - row * FK;
+        s_feat[k] = (f < F && a0 + row < n) ? feat[(size_t)(a0 + row) * F + f] : 0.0f;
+    }
+}
+// acc[j] = the feature embedding, K = FK, all eight waves (output tile w, four agent tiles); we: [FK / 8][8 tiles][64]
+__device__ __forceinline__ void dense_emb(f32x16 (&acc)[4], const float *s_feat, const f32x4 *we, int FK) {
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc[j] = f32x16{0};
+    for (int m = 0; m < FK / 8; m++) {
+        const f32x4 wm = we[((size_t)m * 8 + w) * 64 + l];
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const f32x4 x = *(const f32x4 *)(s_feat + (32 * j + r32) * FK + 8 * m + 4 * g);
+            acc[j] = mfma4(wm, x, acc[j]);
+        }
+    }
+}
+// relu(acc + bias) -> sink(j, r32, w, q, g, v): lane (agent 32 j + r32, g) of output tile w holds units 32 w + 8 q + 4 g + 0..3 (bias: [256], natural order)
+template <class Sink>
+__device__ __forceinline__ void hidden_out(const f32x16 (&acc)[4], const float *bias, const Sink &sink) {
+    const int tid = threadIdx.x, l = tid & 63, w = tid >> 6, g = l >> 5, r32 = l & 31;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const f32x4 b = *(const f32x4 *)(bias + 32 * w + 8 * q + 4 * g);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const f32x4 v = {relu(acc[j][4 * q] + b[0]), relu(acc[j][4 * q + 1] + b[1]), relu(acc[j][4 * q + 2] + b[2]), relu(acc[j][4 * q + 3] + b[3])};
+            sink(j, r32, w, q, g, v);
+        }
+    }
+}
+struct ToX {          // half `half` of x float[n][512], agents a0 .. of the workgroup; rows past n are not stored
+    float *x;
+    int a0, n, half;
+    __device__ __forceinline__ void operator()(int j, int r32, int w, int q, int g, const f32x4 &v) const {
+        if (a0 + 32 * j + r32 < n) *(f32x4 *)(x + (size_t)(a0 + 32 * j + r32) * 512 + 256 * half + 32 * w + 8 * q + 4 * g) = v;
+    }
+};
+struct ToHid {        // the LDS image of one half of the hidden layer, [128 agents][64 units] (hid_slot)
+    f32x4 *s_hid;
+    __device__ __forceinline__ void operator()(int j, int r32, int w, int q, int g, const f32x4 &v) const { s_hid[hid_slot(32 * j + r32, 8 * w + 2 * q + g)] = v; }
+};
+
+// ---------------------------------------------------------------------------------------------------- the heads
+// [32 outputs] x [32 agents] of one wave over K = 512: wh = the packed head ([64 groups][64 lanes]), l the lane, hp = the agent's row + g
+// (group m at hp[2 m]); the operands of the next group load while the current one's four MFMAs run
+__device__ __forceinline__ f32x16 head_gemm512(const f32x4 *wh, int l, const f32x4 *hp) {
+    f32x16 acc = {0};
+    f32x4 hw[2], hx[2];
+    hw[0] = wh[l];
+    hx[0] = hp[0];
+    for (int m = 0; m < 64; m++) {
+        if (m + 1 < 64) { hw[(m + 1) & 1] = wh[(m + 1) * 64 + l]; hx[(m + 1) & 1] = hp[2 * (m + 1)]; }
+        acc = mfma4(hw[m & 1], hx[m & 1], acc);
+    }
+    return acc;
+}
+// The Q row of a lane pair and its action.  Lane (agent, g) holds outputs out_of(r, g) of h; its partner lane ^ 32 the other sixteen.
+// dueling: outputs 0..n_action-1 are the advantage, output n_action the value, Q = h + shift_of(value, sum of the advantages) -- the shift
+// is the caller's arithmetic; else Q = h.  The action is the argmax of the Q row itself in torch.argmax's order (q_before): a NaN anywhere
+// in the network reaches the row, and then its first NaN is chosen, as the PyTorch path chooses it; every action lies in [0, n_action)
+// whatever the input.  live lanes store the action (g == 0) and, if q, their outputs of the row.  Whole waves call this (shuffles).
+template <class ShiftOf>
+__device__ __forceinline__ void q_epilogue(const f32x16 &h, int g, int n_action, bool dueling, const ShiftOf &shift_of, bool live, int agent,
+                                           int *actions, float *q) {
+    float shift = 0.0f;
+    if (dueling) {
+        float sum = 0.0f, value = 0.0f;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+            const int o = out_of(r, g);
+            if (o < n_action) sum += h[r];
+            if (o == n_action) value = h[r];
+        }
+        sum += __shfl_xor(sum, 32);
+        value += __shfl_xor(value, 32);
+        shift = shift_of(value, sum);
+    }
+    float best = -INFINITY;
+    int arg = n_action;           // (not an action: every output of the row comes before it)
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = out_of(r, g);
+        if (o < n_action && q_before(h[r] + shift, o, best, arg)) { best = h[r] + shift; arg = o; }
+    }
+    const float obest = __shfl_xor(best, 32);
+    const int oarg = __shfl_xor(arg, 32);
+    if (q_before(obest, oarg, best, arg)) { best = obest; arg = oarg; }
+    if (live) {
+        if (g == 0) actions[agent] = arg;
+        if (q) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) { const int o = out_of(r, g); if (o < n_action) q[(size_t)agent * n_action + o] = h[r] + shift; }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- streamed rows
+// NC chunks of operands through two register buffers: the next chunk loads while the current one's MFMAs run (NC even)
+template <int NC, class Buf, class Load, class Run>
+__device__ __forceinline__ void pingpong(Buf (&op)[2], const Load &load, const Run &run) {
+    load(0, op[0]);
+    for (int c = 0; c < NC; c += 2) {
+        load(c + 1, op[1]);
+        run(op[0]);
+        if (c + 2 < NC) load(c + 2, op[0]);
+        run(op[1]);
+    }
 }
 
 // The DQN's trunk for the DRQN: k_dqn_conv_f32, then k_dqn_head_f32 stopped after its hidden layer, which it stores as

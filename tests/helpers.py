@@ -32,6 +32,101 @@ def ensure_emu():
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 
+def build_policy_emu(name, sources, headers, caller):
+    """`sources` (of magent_amd/csrc) compiled as plain C++ against tests/hipemu (hipemu.build's compiler, flags and LDS rewrite) into a
+    library of their own, tests/hipemu/_build/<name>/lib<name>_emu.so; `headers` are copied beside them so that nothing stale from the
+    engine's emulated build is found first.  Rebuilt when a source, a header, the emulator, this file or `caller` (the test file) is newer."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
+    import build as emu_build
+    import fcntl
+    csrc = emu_build.CSRC
+    out = os.path.join(ROOT, "tests", "hipemu", "_build", name)
+    lib = os.path.join(out, "lib%s_emu.so" % name)
+    deps = [os.path.join(csrc, f) for f in headers + sources] + [
+        os.path.join(ROOT, "include", "magent_policy.h"), os.path.join(emu_build.HERE, "emu_runtime.cc"),
+        os.path.join(emu_build.HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__), os.path.abspath(caller)]
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if os.path.exists(lib) and all(os.path.getmtime(d) <= os.path.getmtime(lib) for d in deps):
+            return lib
+        sub = lambda text: emu_build.DYN.sub(lambda m: "%s *%s = (%s *)hipemu::dynamic_lds();" % (m.group(1), m.group(2), m.group(1)),
+                                             text).replace('"../../include/', '"')
+        for h in headers:
+            src = os.path.join(csrc, h)
+            open(os.path.join(out, h), "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
+        objs = []
+        for f in sources:
+            src = os.path.join(csrc, f)
+            cc = os.path.join(out, f.replace(".hip", "_emu.cc"))
+            open(cc, "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
+            objs.append(cc.replace(".cc", ".o"))
+            subprocess.check_call([emu_build.CXX] + emu_build.FLAGS + ["-c", cc, "-o", objs[-1]])
+        objs.append(os.path.join(out, "emu_runtime.o"))
+        subprocess.check_call([emu_build.CXX] + emu_build.FLAGS + ["-c", os.path.join(emu_build.HERE, "emu_runtime.cc"), "-o", objs[-1]])
+        tmp = lib + ".%d.tmp" % os.getpid()
+        subprocess.check_call([emu_build.CXX, "-shared", "-fPIC", "-o", tmp] + objs + ["-Wl,-Bsymbolic", "-lpthread"])
+        os.replace(tmp, lib)
+    return lib
+
+
+class PolicyLeg(object):
+    """one of the two legs of a policy-kernel test.  `emu`: an emulated build (`emu_lib()` returns its path) on CPU tensors, with
+    MAGENT_TUNE=`tune` if given (read at the library's first call); `gpu`: the product library on cuda:0.
+    policy(...): the leg's `policy_class` of hip_policy (the emulated leg hands it its library)."""
+
+    def __init__(self, name, emu_lib, tune=None, policy_class=None):
+        import ctypes
+        import torch
+        from magent_amd import c_lib
+        self.name, self.policy_class = name, policy_class
+        if name == "emu":
+            if tune:
+                os.environ.setdefault("MAGENT_TUNE", tune)
+            self.lib = c_lib.declare_policy(ctypes.CDLL(emu_lib(), mode=os.RTLD_LOCAL))
+            self.dev = torch.device("cpu")
+        else:
+            self.lib = c_lib.load()
+            self.dev = torch.device("cuda", 0)
+
+    def policy(self, net, vs, feat, A, chunk=131072):
+        from magent_amd.builtin.torch_model import hip_policy
+        return getattr(hip_policy, self.policy_class)(net, vs, (feat,), A, self.dev, chunk=chunk, lib=self.lib if self.name == "emu" else None)
+
+    def sync(self):
+        import torch
+        if self.dev.type == "cuda":
+            torch.cuda.synchronize()
+
+
+def policy_legs(emu_lib, tune=None, policy_class=None):
+    """(leg, LEGS) of a test module: leg(name) makes the module's PolicyLeg at first use; LEGS parametrises a test over both legs"""
+    import pytest
+    made = {}
+
+    def leg(name):
+        if name not in made:
+            made[name] = PolicyLeg(name, emu_lib, tune, policy_class)
+        return made[name]
+    return leg, ["emu", pytest.param("gpu", marks=pytest.mark.gpu)]
+
+
+def make_policy_inputs(view_space, feat, n, seed, extra=0, fill=0.0):
+    """observation-like view (sparse, fractions) and features [n + extra]; the `extra` rows behind the n agents hold `fill`"""
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    view = (torch.rand((n + extra,) + view_space, generator=g) < 0.3).float() * torch.rand((n + extra,) + view_space, generator=g)
+    featv = torch.rand((n + extra, feat), generator=g) * 2 - 0.5
+    view[n:] = fill
+    featv[n:] = fill
+    return view, featv
+
+
+def net_params(net):
+    """a module's state_dict as float64 NumPy arrays"""
+    return {k: v.detach().cpu().double().numpy() for k, v in net.state_dict().items()}
+
+
 def merge_env(*dicts):
     """environment dicts merged; MAGENT_TUNE entries (magent_amd/csrc/tune.h: "key=value,key=value") are joined, not overwritten"""
     out = {}

@@ -10,19 +10,14 @@ by n instead of n - 1 (the supported-region sweep, CommNet spans the call); the 
 one-hot rows of the draw test overflow to NaN); c_a >= t instead of c_a > t (p = [0.5, 0.5], u = 0.5); an fmaxf ReLU (a NaN in a view)."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import helpers as H
 
-ROOT = H.ROOT
 NAN, INF = float("nan"), float("inf")
 HID = 512
-EMU_DIR = os.path.join(ROOT, "tests", "hipemu", "_build", "a2c")
-EMU_LIB = os.path.join(EMU_DIR, "liba2c_emu.so")
 
 # The working bounds of the probabilities (absolute) and of the value (relative to 1 + the case's largest |value|).  Measured on the CPU:
 # the worst error of the PyTorch float32 CPU forward of _ActorCritic against the float64 oracle below over CASES x {plain, CommNet} was
@@ -34,76 +29,12 @@ P_WORK, V_WORK = ORDER_FACTOR * TORCH_P_ERR, ORDER_FACTOR * TORCH_V_ERR
 
 
 def build_a2c_emu():
-    """policy_a2c_f32.hip compiled as plain C++ against tests/hipemu (hipemu.build's compiler, flags and LDS rewrite) into a library of its
-    own; its header is copied beside it so that nothing stale from the engine's emulated build is found first"""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
-    import build as emu_build
-    import fcntl
-    csrc = emu_build.CSRC
-    headers = ["policy_f32_dev.h"]
-    sources = ["policy_a2c_f32.hip"]
-    deps = [os.path.join(csrc, f) for f in headers + sources] + [
-        os.path.join(ROOT, "include", "magent_policy.h"), os.path.join(emu_build.HERE, "emu_runtime.cc"),
-        os.path.join(emu_build.HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__)]
-    os.makedirs(EMU_DIR, exist_ok=True)
-    with open(os.path.join(EMU_DIR, ".lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if os.path.exists(EMU_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(EMU_LIB) for d in deps):
-            return EMU_LIB
-        sub = lambda text: emu_build.DYN.sub(lambda m: "%s *%s = (%s *)hipemu::dynamic_lds();" % (m.group(1), m.group(2), m.group(1)),
-                                             text).replace('"../../include/', '"')
-        for h in headers:
-            src = os.path.join(csrc, h)
-            open(os.path.join(EMU_DIR, h), "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
-        objs = []
-        flags = emu_build.FLAGS
-        for f in sources:
-            src = os.path.join(csrc, f)
-            cc = os.path.join(EMU_DIR, f.replace(".hip", "_emu.cc"))
-            open(cc, "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
-            objs.append(cc.replace(".cc", ".o"))
-            subprocess.check_call([emu_build.CXX] + flags + ["-c", cc, "-o", objs[-1]])
-        objs.append(os.path.join(EMU_DIR, "emu_runtime.o"))
-        subprocess.check_call([emu_build.CXX] + flags + ["-c", os.path.join(emu_build.HERE, "emu_runtime.cc"), "-o", objs[-1]])
-        tmp = EMU_LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([emu_build.CXX, "-shared", "-fPIC", "-o", tmp] + objs + ["-Wl,-Bsymbolic", "-lpthread"])
-        os.replace(tmp, EMU_LIB)
-    return EMU_LIB
+    """policy_a2c_f32.hip as a library of its own (helpers.build_policy_emu)"""
+    return H.build_policy_emu("a2c", ["policy_a2c_f32.hip"], ["policy_f32_dev.h", "policy_host.h"], __file__)
 
 
-# ---------------------------------------------------------------------------------------------------- the two legs
-class Leg(object):
-    def __init__(self, name):
-        import torch
-        from magent_amd import c_lib
-        self.name = name
-        if name == "emu":
-            self.lib = c_lib.declare_policy(ctypes.CDLL(build_a2c_emu(), mode=os.RTLD_LOCAL))
-            self.dev = torch.device("cpu")
-        else:
-            self.lib = c_lib.load()
-            self.dev = torch.device("cuda", 0)
-
-    def policy(self, net, vs, feat, A, chunk=131072):
-        from magent_amd.builtin.torch_model.hip_policy import HipA2cPolicyF32
-        return HipA2cPolicyF32(net, vs, (feat,), A, self.dev, chunk=chunk, lib=self.lib if self.name == "emu" else None)
-
-    def sync(self):
-        import torch
-        if self.dev.type == "cuda":
-            torch.cuda.synchronize()
-
-
-_LEGS = {}
-
-
-def leg(name):
-    if name not in _LEGS:
-        _LEGS[name] = Leg(name)
-    return _LEGS[name]
-
-
-LEGS = ["emu", pytest.param("gpu", marks=pytest.mark.gpu)]
+leg, LEGS = H.policy_legs(build_a2c_emu, policy_class="HipA2cPolicyF32")      # the two legs
+make_inputs, net_params = H.make_policy_inputs, H.net_params
 COMM = [pytest.param(False, id="plain"), pytest.param(True, id="comm")]
 
 
@@ -118,13 +49,6 @@ def make_net(vs, feat, A, comm, seed, dev="cpu", scale=3.0):
     return net.to(dev)
 
 
-def make_inputs(vs, feat, n, seed):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    view = (torch.rand((n,) + vs, generator=g) < 0.3).float() * torch.rand((n,) + vs, generator=g)
-    return view, torch.rand((n, feat), generator=g) * 2 - 0.5
-
-
 def run(lg, pol, view, featv, u=None):
     import torch
     out = pol.infer(view.to(lg.dev).contiguous(), featv.to(lg.dev).contiguous(), u=None if u is None else torch.as_tensor(u).to(lg.dev),
@@ -134,10 +58,6 @@ def run(lg, pol, view, featv, u=None):
 
 
 # ---------------------------------------------------------------------------------------------------- float64 and the derived bound
-def net_params(net):
-    return {k: v.detach().cpu().double().numpy() for k, v in net.state_dict().items()}
-
-
 def np_a2c(P, view, feature, comm):
     """_ActorCritic.forward in float64 -> (p [n][A], value [n]); relu is np.maximum (a NaN stays a NaN)"""
     p, v, _ = _np_a2c(P, view, feature, comm, False)

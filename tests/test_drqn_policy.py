@@ -10,92 +10,24 @@ sweep); the first duplicate stored instead of the last, a stale table after n ==
 inputs and weights)."""
 import ctypes
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import helpers as H
 
-ROOT = H.ROOT
 NAN, INF = float("nan"), float("inf")
 S = 512
-EMU_DIR = os.path.join(ROOT, "tests", "hipemu", "_build", "drqn")
-EMU_LIB = os.path.join(EMU_DIR, "libdrqn_emu.so")
 
 
 def build_drqn_emu():
-    """policy_f32.hip + policy_drqn_f32.hip compiled as plain C++ against tests/hipemu (hipemu.build's compiler, flags and LDS rewrite) into
-    a library of their own; their headers are copied beside them so that nothing stale from the engine's emulated build is found first"""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "hipemu"))
-    import build as emu_build
-    import fcntl
-    csrc = emu_build.CSRC
-    headers = ["policy_f32_dev.h", "tune.h"]
-    sources = ["policy_f32.hip", "policy_drqn_f32.hip"]
-    deps = [os.path.join(csrc, f) for f in headers + sources] + [
-        os.path.join(ROOT, "include", "magent_policy.h"), os.path.join(emu_build.HERE, "emu_runtime.cc"),
-        os.path.join(emu_build.HERE, "hip", "hip_runtime.h"), os.path.abspath(__file__)]
-    os.makedirs(EMU_DIR, exist_ok=True)
-    with open(os.path.join(EMU_DIR, ".lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        if os.path.exists(EMU_LIB) and all(os.path.getmtime(d) <= os.path.getmtime(EMU_LIB) for d in deps):
-            return EMU_LIB
-        sub = lambda text: emu_build.DYN.sub(lambda m: "%s *%s = (%s *)hipemu::dynamic_lds();" % (m.group(1), m.group(2), m.group(1)),
-                                             text).replace('"../../include/', '"')
-        for h in headers:
-            src = os.path.join(csrc, h)
-            open(os.path.join(EMU_DIR, h), "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
-        objs = []
-        for f in sources:
-            src = os.path.join(csrc, f)
-            cc = os.path.join(EMU_DIR, f.replace(".hip", "_emu.cc"))
-            open(cc, "w").write('#line 1 "%s"\n' % src + sub(open(src).read()))
-            objs.append(cc.replace(".cc", ".o"))
-            subprocess.check_call([emu_build.CXX] + emu_build.FLAGS + ["-c", cc, "-o", objs[-1]])
-        objs.append(os.path.join(EMU_DIR, "emu_runtime.o"))
-        subprocess.check_call([emu_build.CXX] + emu_build.FLAGS + ["-c", os.path.join(emu_build.HERE, "emu_runtime.cc"), "-o", objs[-1]])
-        tmp = EMU_LIB + ".%d.tmp" % os.getpid()
-        subprocess.check_call([emu_build.CXX, "-shared", "-fPIC", "-o", tmp] + objs + ["-Wl,-Bsymbolic", "-lpthread"])
-        os.replace(tmp, EMU_LIB)
-    return EMU_LIB
+    """policy_f32.hip + policy_drqn_f32.hip as a library of their own (helpers.build_policy_emu)"""
+    return H.build_policy_emu("drqn", ["policy_f32.hip", "policy_drqn_f32.hip"], ["policy_f32_dev.h", "policy_host.h", "tune.h"], __file__)
 
 
-# ---------------------------------------------------------------------------------------------------- the two legs
-class Leg(object):
-    def __init__(self, name):
-        import torch
-        from magent_amd import c_lib
-        self.name = name
-        if name == "emu":
-            os.environ.setdefault("MAGENT_TUNE", "policy_grid=3")      # (read at the library's first call: three conv workgroups walk every tile)
-            self.lib = c_lib.declare_policy(ctypes.CDLL(build_drqn_emu(), mode=os.RTLD_LOCAL))
-            self.dev = torch.device("cpu")
-        else:
-            self.lib = c_lib.load()
-            self.dev = torch.device("cuda", 0)
-
-    def policy(self, net, vs, feat, A, chunk=131072):
-        from magent_amd.builtin.torch_model.hip_policy import HipDrqnPolicyF32
-        return HipDrqnPolicyF32(net, vs, (feat,), A, self.dev, chunk=chunk, lib=self.lib if self.name == "emu" else None)
-
-    def sync(self):
-        import torch
-        if self.dev.type == "cuda":
-            torch.cuda.synchronize()
-
-
-_LEGS = {}
-
-
-def leg(name):
-    if name not in _LEGS:
-        _LEGS[name] = Leg(name)
-    return _LEGS[name]
-
-
-LEGS = ["emu", pytest.param("gpu", marks=pytest.mark.gpu)]
+# the two legs; on the emulator three conv workgroups walk every tile
+leg, LEGS = H.policy_legs(build_drqn_emu, tune="policy_grid=3", policy_class="HipDrqnPolicyF32")
+make_inputs, net_params = H.make_policy_inputs, H.net_params
 
 
 def make_rnet(vs, feat, A, dueling, seed, dev="cpu", scale=3.0):
@@ -109,18 +41,7 @@ def make_rnet(vs, feat, A, dueling, seed, dev="cpu", scale=3.0):
     return q.to(dev)
 
 
-def make_inputs(vs, feat, n, seed):
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    view = (torch.rand((n,) + vs, generator=g) < 0.3).float() * torch.rand((n,) + vs, generator=g)
-    return view, torch.rand((n, feat), generator=g) * 2 - 0.5
-
-
 # ---------------------------------------------------------------------------------------------------- float64
-def net_params(net):
-    return {k: v.detach().cpu().double().numpy() for k, v in net.state_dict().items()}
-
-
 def np_drqn_step(P, view, feature, h, dueling, magnitude=False):
     """one step of _RecurrentQNet.forward (batch n, unroll 1) in float64 -> (Q [n][A], h' [n][512]).  relu is np.maximum (a NaN stays NaN).
     magnitude=True: the trunk and the gates' pre-activations on |weights|, |biases|, |inputs|, |h| -> (Xmag, Gmag [4][n][512]) for the bound"""

@@ -22,39 +22,9 @@ NAN, INF = float("nan"), float("inf")
 
 
 # ---------------------------------------------------------------------------------------------------- the two legs
-class Leg(object):
-    """`emu`: the emulated build on CPU tensors; `gpu`: the product library on cuda:0"""
-
-    def __init__(self, name):
-        import torch
-        self.name = name
-        if name == "emu":
-            os.environ.setdefault("MAGENT_TUNE", "policy_grid=3")      # (read at the emulated library's first call: three workgroups walk every tile)
-            self.lib = ctypes.CDLL(H.ensure_emu())
-            self.dev = torch.device("cpu")
-        else:
-            from magent_amd import c_lib
-            self.lib = c_lib.load()
-            self.dev = torch.device("cuda", 0)
-        for f in ("policy_dqn_infer_f32", "policy_dqn_infer", "policy_dqn_infer_bf16", "policy_dqn_f32_supported", "policy_dqn_supported"):
-            getattr(self.lib, f).restype = ctypes.c_int
-
-    def sync(self):
-        import torch
-        if self.dev.type == "cuda":
-            torch.cuda.synchronize()
-
-
-_LEGS = {}
-
-
-def leg(name):
-    if name not in _LEGS:
-        _LEGS[name] = Leg(name)
-    return _LEGS[name]
-
-
-LEGS = ["emu", pytest.param("gpu", marks=pytest.mark.gpu)]
+# `emu`: the engine-wide emulated build on CPU tensors (three workgroups walk every tile); `gpu`: the product library on cuda:0
+leg, LEGS = H.policy_legs(H.ensure_emu, tune="policy_grid=3")
+make_inputs = H.make_policy_inputs
 
 
 def make_qnet(view_space, feat, n_action, seed, dev="cpu", scale=3.0):
@@ -66,17 +36,6 @@ def make_qnet(view_space, feat, n_action, seed, dev="cpu", scale=3.0):
         for p in q.parameters():          # larger weights than the default init: every layer's output matters in Q
             p.mul_(scale)
     return q.to(dev)
-
-
-def make_inputs(view_space, feat, n, seed, extra=0, fill=0.0):
-    """observation-like view (sparse, fractions) and features [n + extra]; the `extra` rows behind the n agents hold `fill`"""
-    import torch
-    g = torch.Generator().manual_seed(seed)
-    view = (torch.rand((n + extra,) + view_space, generator=g) < 0.3).float() * torch.rand((n + extra,) + view_space, generator=g)
-    featv = torch.rand((n + extra, feat), generator=g) * 2 - 0.5
-    view[n:] = fill
-    featv[n:] = fill
-    return view, featv
 
 
 def policy(lg, kind, qnet, view_space, feat, n_action):
