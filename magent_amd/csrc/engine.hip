@@ -275,8 +275,7 @@ void Env::use_device() { HIP_OK(hipSetDevice(device_id)); }
 //   * an observation of a group whose actions are already set joins and commits last_action first (the feature rows show it).
 bool Env::side_wanted() {
     if (!overlap_enabled || checked_step || host_shuffle || !first_render || (turn_mode && any_multicell)) return false;
-    int total_n = 0;
-    for (auto &g : groups) total_n += g.n;
+    const int total_n = total_agents();
     return total_n > 0 && !solo_ok(total_n);
 }
 void Env::mark_state() {

@@ -14,23 +14,29 @@ bool Env::cycle_eligible(int n_group, float *const *view, float *const *feat, in
     if (!device_ready) fatal("cycle called before reset");
     const int NG = (int)groups.size();
     if (n_group != NG) fatal("env_cycle_many: n_group (%d) differs from the number of groups (%d)", n_group, NG);
-    int total_n = 0;
-    for (auto &g : groups) total_n += g.n;
-    bool fused = solo_ok(total_n) && !step_pending && !serial_calls_on;   // (a group given actions twice: the literal loop, by the call sequence)
+    // (a group given actions twice: the literal loop, by the call sequence)
     // the observed groups must share one minimap (same window, same "skip absorbed" rule) to be rendered by one launch
+    return solo_ok(total_agents()) && !step_pending && !serial_calls_on && observed_groups_ok(view, feat, true, false, first_obs_out);
+}
+
+// Can one launch render the observed groups (a view buffer and agents) of a cycle?  Every one has a feature buffer too, both 16-byte aligned;
+// under minimap_mode all of them look through the same window -- goals_differ: and agree on can_absorb, the minimap's "skip the goals taken"
+// rule (the two-launch cycle; the pipeline takes no world with goals); at most RENDER_MULTI_MAX of them.  refuse_acted: no group has been
+// given its actions by env_set_action_device already (the pipeline leaves that to the call sequence).  *first_obs_out: the first such group
+bool Env::observed_groups_ok(float *const *view, float *const *feat, bool goals_differ, bool refuse_acted, int *first_obs_out) const {
     int n_obs = 0, first_obs = -1;
-    for (int g = 0; g < NG && fused; g++) {
+    if (first_obs_out) *first_obs_out = -1;
+    for (int g = 0; g < (int)groups.size(); g++) {
+        if (refuse_acted && groups[g].acted) return false;
         if (!(view && view[g]) || groups[g].n == 0) continue;
-        if (!feat || !feat[g] || (((uintptr_t)view[g]) & 15) || (((uintptr_t)feat[g]) & 15)) fused = false;
+        if (!feat || !feat[g] || (((uintptr_t)view[g]) & 15) || (((uintptr_t)feat[g]) & 15)) return false;
+        const HostType &t = *groups[g].type, &t0 = *groups[first_obs < 0 ? g : first_obs].type;
+        if (minimap_mode && (t.view.height != t0.view.height || t.view.width != t0.view.width || (goals_differ && t.can_absorb != t0.can_absorb))) return false;
         if (first_obs < 0) first_obs = g;
-        else if (minimap_mode && (groups[g].type->view.height != groups[first_obs].type->view.height ||
-                                  groups[g].type->view.width != groups[first_obs].type->view.width ||
-                                  groups[g].type->can_absorb != groups[first_obs].type->can_absorb)) fused = false;
         n_obs++;
     }
-    if (n_obs > RENDER_MULTI_MAX) fused = false;
     if (first_obs_out) *first_obs_out = first_obs;
-    return fused;
+    return n_obs <= RENDER_MULTI_MAX;
 }
 
 bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, BatchItem &item) {
@@ -42,8 +48,6 @@ bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, con
     move_nodes();
     alive_valid = false;            // (the one-launch cycle compacts by itself)
     const int NG = (int)groups.size();
-    int total_n = 0;
-    for (auto &g : groups) total_n += g.n;
     WorldView &W = item.W;
     W = this->view();
     // ---- launch 1: the observations of every observed group
@@ -60,27 +64,19 @@ bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, con
         M.blocks[k] = M.P[k].spans + M.P[k].feat_blocks;
     }
     // ---- launch 2: set_action, step, get_reward, clear_dead, the next minimap
-    shuffle_buffers(total_n);
+    step_kind = StepKind::Solo;
+    shuffle_buffers(total_agents());
     push_rng();
-    scratch_for(0);
-    {   // groups that were given their actions by env_set_action_device before this call (a NULL entry in `actions`): when the world was
-        // beyond the one-launch step's limit for an environment on its own (but within the batch's), that call left tile counts -- the
-        // sequence numbers and the attack list's length are written out here, as Env::step_begin does
-        bool first = true;
-        for (int g = 0; g < NG; g++)
-            if (groups[g].sa_off >= 0) { launch_seq_assign(stream, W, g, d_asums, d_wpre, groups[g].sa_off, first); first = false; groups[g].sa_off = -1; }
-        step_calls.clear();
-    }
+    scratch_for(Scratch::Solo);
+    // groups that were given their actions by env_set_action_device before this call (a NULL entry in `actions`): when the world was
+    // beyond the one-launch step's limit for an environment on its own (but within the batch's), that call left tile counts
+    assign_pending_seq(W);
+    for (auto &G : groups) G.sa_off = -1;
+    step_calls.clear();
     step_live_paint = live_paint_now = paint_valid;
     W.live_paint = step_live_paint ? 1 : 0;
-    const ShuffleBufs B = shuffle_bufs();
     SoloStep &S = item.S;
-    S = SoloStep{};
-    S.shead = B.head; S.sfirst = B.first; S.sj = B.j; S.slink = B.link;
-    S.rank = d_rank; S.powtab = d_powtab; S.hit = d_hit;
-    S.rules = d_rule_args; S.progs = d_rule_progs; S.n_rules = (int)rule_args.size();
-    S.kmax = attack_kmax; S.nt_eval = solo_nt_eval; S.max_rounds = 1 << 20;
-    S.rec = h_rec; S.seq = ++step_seq;
+    S = solo_step_args();
     for (int g = 0; g < NG; g++) {
         HostGroup &G = groups[g];
         if (actions && actions[g]) {
@@ -89,7 +85,7 @@ bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, con
             if (G.n > 0) { S.actions[g] = actions[g]; S.call_base[g] = move_seq_base; move_seq_base += G.n; }
         }
         if (rewards && rewards[g] && G.n > 0) { S.rewards[g] = rewards[g]; S.group_reward[g] = G.group_reward; }
-        S.dst[g] = {G.alt.x, G.alt.y, G.alt.id, G.alt.last_action, G.alt.hp, G.alt.next_reward, G.alt.last_reward, G.alt.absorbed, G.alt.dir};
+        S.dst[g] = G.alt_arrays();
     }
     S.do_clear = 1;
     S.gtab_out = d_gtab; S.ttab_out = d_ttab;
@@ -104,43 +100,14 @@ bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, con
 
 void Env::cycle_finish(int *done) {
     use_device();
-    const int NG = (int)groups.size();
     wait_record(step_seq);
     const StepRecord &r = *h_rec;
-    if (r.error) fatal("%s resolution did not converge", r.error == 1 ? "attack" : "move");
-    if (r.unsupported) fatal("internal: a can_absorb agent moved on the parallel path (a set_action for goals switches the step to the literal loop)");
-    if (r.pack_overflow) fatal("internal: hp / type.hp outside [0, 2) met the packed view-cell format");
-    if (r.bad_action) fatal("set_action: an action outside [0, n_action) (the reference indexes its tables out of range here)");
-    if (r.hit_overflow) fatal("a target collected more attack hits than the engine's hit lists hold (256)");
-    if (rng_on_device) rng.x = r.rng;
     last_attack_iters = r.rounds_attack; last_move_iters = r.rounds_move; attack_round = r.rounds_attack;
-    int live = 0;
-    for (int g = 0; g < NG; g++) {
-        HostGroup &G = groups[g];
-        G.acted = false;
-        G.group_reward = 0;
-        if (G.n - r.dead[g] > 0) live++;
-        const int gone = r.dead[g] + r.taken[g];
-        if (gone > 0 && G.n > 0) {   // the survivors' arrays have changed places
-            std::swap(G.cur.x, G.alt.x); std::swap(G.cur.y, G.alt.y); std::swap(G.cur.id, G.alt.id);
-            std::swap(G.cur.hp, G.alt.hp); std::swap(G.cur.last_action, G.alt.last_action);
-            std::swap(G.cur.last_reward, G.alt.last_reward); std::swap(G.cur.next_reward, G.alt.next_reward);
-            std::swap(G.cur.absorbed, G.alt.absorbed); std::swap(G.cur.dir, G.alt.dir);
-            G.n -= gone;
-        }
-        G.h_dead = 0; G.h_taken = 0;
-        G.indexed = G.n;
-    }
-    *done = live < NG;   // GridWorld.cc:619-624
-    for (size_t k = 0; k < rules.size(); k++) if (((r.triggers >> k) & 1ull) && rules[k].terminal) *done = 1;
-    stale_events = false;      // (the cycle's own clear_dead has reset every last_op)
-    move_seq_base = 0;
-    h_occ_valid = false;
+    finish_step(r, done);
+    // the cycle's own clear_dead (it has reset every last_op, refreshed the device tables and made the next minimap)
     tables_valid = true;
-    paint_valid = step_live_paint;
-    live_paint_now = false;
-    mini_valid = cyc_next_mini;
-    if (cyc_next_mini) { mini_vh = cyc_mini_vh; mini_vw = cyc_mini_vw; mini_skip = cyc_mini_skip; mini_pop = mini_population(cyc_mini_skip); }
+    if (cyc_next_mini) { mini_vh = cyc_mini_vh; mini_vw = cyc_mini_vw; mini_skip = cyc_mini_skip; }
+    after_clear(take_survivors(), cyc_next_mini);
 }
 
 void Env::cycle(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, int *done) {
@@ -219,11 +186,8 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
         lead.use_device();
         if ((size_t)n_env > lead.batch_cap) {
             HIP_OK(hipStreamSynchronize(lead.stream));
-            if (lead.batch_h) HIP_OK(hipHostFree(lead.batch_h));
-            dfree(lead.arena, lead.batch_d);
             lead.batch_cap = std::max<size_t>((size_t)n_env, lead.batch_cap * 2);
-            HIP_OK(hipHostMalloc((void **)&lead.batch_h, sizeof(BatchItem) * lead.batch_cap, hipHostMallocDefault));
-            HIP_OK(dev_malloc(lead.arena, &lead.batch_d, sizeof(BatchItem) * lead.batch_cap));
+            renew_pair(lead.arena, lead.batch_h, lead.batch_d, lead.batch_cap);
         }
         // item e describes environment e (an environment that does not take the two-launch cycle leaves a skip marker).  A description costs
         // ~0.2 us of host time (measured: 28 us for 128 environments) -- sharing them out over threads cost more than it saved.
@@ -255,14 +219,9 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
         lead.use_device();
         if ((size_t)n_env > lead.pipe_cap) {
             HIP_OK(hipStreamSynchronize(lead.stream));
-            if (lead.pipe_h) HIP_OK(hipHostFree(lead.pipe_h));
-            if (lead.reports_h) HIP_OK(hipHostFree(lead.reports_h));
-            dfree(lead.arena, lead.pipe_d); dfree(lead.arena, lead.reports_d);
             lead.pipe_cap = std::max<size_t>((size_t)n_env, lead.pipe_cap * 2);
-            HIP_OK(hipHostMalloc((void **)&lead.pipe_h, sizeof(PipeItem) * lead.pipe_cap, hipHostMallocDefault));
-            HIP_OK(hipHostMalloc((void **)&lead.reports_h, sizeof(StepRecord) * lead.pipe_cap, hipHostMallocDefault));
-            HIP_OK(dev_malloc(lead.arena, &lead.pipe_d, sizeof(PipeItem) * lead.pipe_cap));
-            HIP_OK(dev_malloc(lead.arena, &lead.reports_d, sizeof(StepRecord) * lead.pipe_cap));
+            renew_pair(lead.arena, lead.pipe_h, lead.pipe_d, lead.pipe_cap);
+            renew_pair(lead.arena, lead.reports_h, lead.reports_d, lead.pipe_cap);
             if (!lead.pipe_ticket) {
                 HIP_OK(dev_malloc(lead.arena, &lead.pipe_ticket, sizeof(int)));
                 HIP_OK(hipMemsetAsync(lead.pipe_ticket, 0, sizeof(int), lead.stream));
@@ -339,12 +298,8 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
         Env &lead = *envs[lead_p];
         lead.use_device();
         // ONE word for the whole batch: k_pipe_finish's last workgroup sets it behind every environment's outputs and reports
-        for (unsigned spins = 0; __atomic_load_n(lead.pipe_flag, __ATOMIC_ACQUIRE) != lead.pipe_flag_seq; spins++)
-            if ((spins & 0x3FFF) == 0x3FFF) {
-                const hipError_t q = hipStreamQuery(lead.stream);
-                if (q == hipSuccess) { if (__atomic_load_n(lead.pipe_flag, __ATOMIC_ACQUIRE) == lead.pipe_flag_seq) break; fatal("the batched cycle finished without publishing its word"); }
-                if (q != hipErrorNotReady) fatal("batched cycle failed: %s", hipGetErrorString(q));
-            }
+        spin_until([&] { return __atomic_load_n(lead.pipe_flag, __ATOMIC_ACQUIRE) == lead.pipe_flag_seq; }, lead.stream,
+                   "the batched cycle finished without publishing its word", "batched cycle");
         if (first) { t3 = std::chrono::steady_clock::now(); first = false; }
         for (size_t k = 0; k < piped.size(); k++) {
             const int e = piped[k];
@@ -367,24 +322,14 @@ bool Env::pipe_eligible(int n_group, float *const *view, float *const *feat, con
     if (!device_ready) fatal("cycle called before reset");
     const int NG = (int)groups.size();
     if (n_group != NG) fatal("env_cycle_many: n_group (%d) differs from the number of groups (%d)", n_group, NG);
-    int total_n = 0;
-    for (auto &g : groups) total_n += g.n;
+    const int total_n = total_agents();
     if (total_out) *total_out = total_n;
     if (!plain_world || checked_step || host_shuffle || !first_render || serial_calls_on || step_pending || rules_on_host || stale_events || total_n == 0) return false;
     if (overlap_enabled) return false;
     if (!fused_rules(rule_args.data(), (int)rule_args.size())) return false;
-    int n_obs = 0, first_obs = -1;
-    for (int g = 0; g < NG; g++) {
-        if (groups[g].acted) return false;                         // (given its actions by env_set_action_device already: the call sequence)
-        if (!(view && view[g]) || groups[g].n == 0) continue;
-        if (!feat || !feat[g] || (((uintptr_t)view[g]) & 15) || (((uintptr_t)feat[g]) & 15)) return false;
-        if (first_obs < 0) first_obs = g;
-        else if (minimap_mode && (groups[g].type->view.height != groups[first_obs].type->view.height || groups[g].type->view.width != groups[first_obs].type->view.width))
-            return false;                                          // (one minimap per environment and cycle)
-        n_obs++;
-    }
     (void)actions;
-    return n_obs <= RENDER_MULTI_MAX;
+    // (a group given its actions by env_set_action_device already: the call sequence; one minimap per environment and cycle)
+    return observed_groups_ok(view, feat, false, true, nullptr);
 }
 
 // are this environment's observed groups of the shape the sweeping render takes?  (Env::cycle_many: one launch form for the whole batch)
@@ -419,8 +364,7 @@ void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, cons
     enter();
     const int NG = (int)groups.size();
     (void)n_group;
-    int total_n = 0;
-    for (auto &g : groups) total_n += g.n;
+    const int total_n = total_agents();
     if (!tables_valid) ensure_tables();
     it.M = RenderMulti{};
     // ---- the observations: worlds whose renders fill the chip by themselves launch their own (launch_render picks the sweeping kernel
@@ -446,10 +390,8 @@ void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, cons
         if (!(actions && actions[g])) continue;
         G.acted = true;
         if (G.n == 0) continue;
-        if ((long long)move_seq_base + G.n >= (1ll << 27)) fatal("more than 2^27 agents given actions in one step");
-        it.actions[g] = actions[g]; it.call_base[g] = move_seq_base; it.P.off[g] = sa_tiles;
-        move_seq_base += G.n;
-        sa_tiles += (G.n + SCAN_TILE_HOST - 1) / SCAN_TILE_HOST;
+        it.actions[g] = actions[g];
+        it.P.off[g] = count_action_call(G, &it.call_base[g]);
     }
     if ((size_t)sa_tiles > asums_cap) {
         grow(arena, d_asums, asums_cap, (size_t)sa_tiles, stream);
@@ -459,9 +401,9 @@ void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, cons
     step_live_paint = live_paint_now = paint_valid;
     step_pending = true;
     map_warm = false;
-    step_was_fast = true; step_was_solo = false; step_was_plain = true; step_fused_rules = true;
+    step_kind = StepKind::Pipeline; step_fused_rules = true;
     plain_steps++;
-    scratch_for(1);
+    scratch_for(Scratch::Plain);
     shuffle_buffers(total_n);
     push_rng();
     attack_round = rounds;
@@ -484,7 +426,7 @@ void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, cons
         HostGroup &G = groups[g];
         if (rewards && rewards[g] && G.n > 0) { it.rewards[g] = rewards[g]; it.group_reward[g] = G.group_reward; }
         it.A.sums_off[g] = alive_off[g];
-        it.A.dst[g] = {G.alt.x, G.alt.y, G.alt.id, G.alt.last_action, G.alt.hp, G.alt.next_reward, G.alt.last_reward, G.alt.absorbed, G.alt.dir};
+        it.A.dst[g] = G.alt_arrays();
     }
     it.A.sums_per_tile = SCAN_TILE_HOST / 256;
     it.alive_sums = d_alive;
@@ -515,27 +457,8 @@ void Env::pipe_after(float *const *rewards, const StepRecord &report, int *done)
         return;
     }
     enter();
-    bool any = false;
-    for (int g = 0; g < NG; g++) {
-        HostGroup &G = groups[g];
-        G.group_reward = 0;
-        const int gone = G.h_dead + G.h_taken;
-        if (gone > 0 && G.n > 0) {       // survivors: double-buffered arrays went to alt, the rest was reset in place
-            std::swap(G.cur.x, G.alt.x); std::swap(G.cur.y, G.alt.y); std::swap(G.cur.id, G.alt.id);
-            std::swap(G.cur.hp, G.alt.hp); std::swap(G.cur.last_action, G.alt.last_action);
-            std::swap(G.cur.last_reward, G.alt.last_reward); std::swap(G.cur.next_reward, G.alt.next_reward);
-            std::swap(G.cur.absorbed, G.alt.absorbed); std::swap(G.cur.dir, G.alt.dir);
-            G.n -= gone;
-            any = true;
-        }
-        G.h_dead = 0; G.h_taken = 0;
-        G.indexed = G.n;
-    }
     tables_valid = true;
-    if (any) { h_occ_valid = false; mini_valid = false; }
-    stale_events = false;
-    alive_valid = false;
-    if (pipe_folded) { mini_valid = true; mini_pop = mini_population(mini_skip); }
+    after_clear(take_survivors(), pipe_folded);
 }
 
 // every environment of a batch shares the first one's stream (kept alive by whoever still uses it)

@@ -73,7 +73,23 @@ struct HostGroup {
     int indexed = 0;             // agents [0, indexed) have been through a clear_dead: Agent::index == position, else 0
     int sa_off = -1;             // this step's set_action call left its tile counts at d_asums[sa_off ...] (SeqPlan); -1: none / one-workgroup form
     PlainGroup pl{};             // scratch of the step of plain games (launch.h)
+    // what clear_dead compacts is double-buffered: the survivors were written to `alt` ...
+    AltArrays alt_arrays() const { return {alt.x, alt.y, alt.id, alt.last_action, alt.hp, alt.next_reward, alt.last_reward, alt.absorbed, alt.dir}; }
+    void take_survivors() {      // ... and the two copies change places (the host's mirror of a compaction of h_dead + h_taken agents)
+        std::swap(cur.x, alt.x); std::swap(cur.y, alt.y); std::swap(cur.id, alt.id);
+        std::swap(cur.hp, alt.hp); std::swap(cur.last_action, alt.last_action);
+        std::swap(cur.last_reward, alt.last_reward); std::swap(cur.next_reward, alt.next_reward);
+        std::swap(cur.absorbed, alt.absorbed); std::swap(cur.dir, alt.dir);
+        n -= h_dead + h_taken;
+        h_dead = h_taken = 0;
+    }
 };
+
+// Which driver runs the pending step (Env::step_begin, pipe_prepare, cycle_prepare set it; step_end, phase_tail, attack_rounds_checked read it):
+// the literal loop | the one-launch step | the single-sync driver over the pipeline of plain games | ... over the generic kernels | host-checked
+enum class StepKind { None, Serial, Solo, Pipeline, Generic, Checked };
+inline bool reports_by_record(StepKind k) { return k != StepKind::None && k != StepKind::Checked; }   // (the pinned StepRecord; else the counter block)
+enum class Scratch { Solo, Plain, Other };       // the three uses of the per-cell scratch words (Env::scratch_for)
 
 struct HostSymbol { int group = 0, index = 0; int ent_g = -1, ent_i = -1; };   // ent_*: the agent the host rule search last bound it to
 struct HostRulePlan { std::vector<int> order, brings; };   // RewardRule::input_symbols / infer_obj (RewardEngine.cc:155-189); -1 = none
@@ -198,10 +214,31 @@ private:
     std::vector<unsigned char> host_triggers;
     void compile_rule_program(size_t k);
     void enqueue_counters();
-    bool step_pending = false, step_was_fast = false, step_was_solo = false, step_live_paint = false, live_paint_now = false;
+    bool step_pending = false, step_live_paint = false, live_paint_now = false;
+    StepKind step_kind = StepKind::None;
     bool solo_ok(int total_n);
+    int total_agents() const { int total_n = 0; for (auto &g : groups) total_n += g.n; return total_n; }
     void serial_add_call(int g, const int *d_act);
+    // the drivers of a step (step_begin picks one) and what they share
     void serial_step();
+    void solo_step(const WorldView &W, int total_n);
+    bool single_sync_step(const WorldView &W, int total_n, bool beside);
+    bool plain_step_tail(const WorldView &W, const PlainWorld &PW);
+    void generic_step_tail(const WorldView &W);
+    void checked_step_run(const WorldView &W, int total_n, bool generic_turns);
+    void move_prep(const WorldView &W, bool starve = true);
+    void move_apply(const WorldView &W);
+    void rules_launch(const WorldView &W);
+    void rules_and_finish(const WorldView &W);
+    void record_attack_events(const int4 *events, int n);
+    SoloStep solo_step_args();
+    void assign_pending_seq(const WorldView &W);
+    int count_action_call(const HostGroup &G, int *base);
+    bool observed_groups_ok(float *const *view, float *const *feat, bool goals_differ, bool refuse_acted, int *first_obs_out) const;
+    StepRecord record_of(const int *counters) const;
+    void finish_step(const StepRecord &r, int *done);
+    bool take_survivors();
+    void after_clear(bool any_compacted, bool next_mini);
     std::vector<SerialCall> serial_calls;   // the calls of a step in which a group was given actions twice (k_step_serial)
     std::vector<int> step_calls;            // groups given actions in this step, in call order
     bool serial_calls_on = false;
@@ -237,10 +274,10 @@ private:
     bool claim_epochs = false;            // ... or written only by steps of the plain pipeline in the current window of epochs (scratch_for)
     unsigned plain_epoch = 0;             // steps of the plain pipeline so far: claim-word epochs and round stamps derive from it
     bool hit_clean = false;               // every hit word is zero (both of those steps keep it so)
-    void scratch_for(int path);
+    void scratch_for(Scratch path);
     int plain_steps = 0, plain_slots = 0;
     int pairs_two_steps = 0, pairs_one_steps = 0, claim_refills = 0;   // (env_get_info "pipeline_stats")
-    bool plain_world = false, step_was_plain = false, step_fused_rules = false, ptab_valid = false;
+    bool plain_world = false, step_fused_rules = false, ptab_valid = false;
     PlainGroup *d_ptab = nullptr;
     int *d_alive = nullptr; size_t alive_cap = 0;      // survivors per 256 agents, left by k_strike for clear_dead (PlainWorld::alive)
     int alive_off[MAXG] = {}, alive_n[MAXG] = {};
@@ -267,7 +304,7 @@ private:
     bool prepare_render(int g, const WorldView &W, RenderArgs &R, RenderPlan &P, float *view, float *feat);
     long long mini_population(bool skip) const;
     MiniArgs mini_args(int vh, int vw, bool skip);
-    bool mini_skip = false, solo_mini = false;
+    bool mini_skip = false;
     void copy_out(void *host_dst, const void *dev_src, size_t bytes);
     void read_back(void *host_dst, const void *dev_src, size_t bytes);
     char *h_small = nullptr; size_t h_small_cap = 0;   // pinned bounce buffer of read_back

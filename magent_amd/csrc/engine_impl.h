@@ -66,6 +66,28 @@ inline void regrow(DevArena &arena, T *&p, size_t old_n, size_t ncap) {
     p = q;
 }
 
+// Wait for a word that a kernel publishes in pinned memory (`ready` loads it, with the ordering its site needs): a stream synchronisation
+// costs several times the PCIe write it waits for; the stream is polled now and then so that a failed launch cannot hang us
+template <class Ready>
+inline void spin_until(Ready ready, hipStream_t stream, const char *unpublished, const char *what) {
+    for (unsigned spins = 0; !ready(); spins++)
+        if ((spins & 0x3FFF) == 0x3FFF) {
+            const hipError_t q = hipStreamQuery(stream);
+            if (q == hipSuccess) { if (ready()) break; fatal("%s", unpublished); }
+            if (q != hipErrorNotReady) fatal("%s failed: %s", what, hipGetErrorString(q));
+        }
+}
+
+// a pinned host array and its device twin of `cap` items, in place of the ones held (the items of a batch, kept by its lead; the caller
+// has waited for the stream that used them)
+template <class T>
+inline void renew_pair(DevArena &arena, T *&h, T *&d, size_t cap) {
+    if (h) HIP_OK(hipHostFree(h));
+    dfree(arena, d);
+    HIP_OK(hipHostMalloc((void **)&h, sizeof(T) * cap, hipHostMallocDefault));
+    HIP_OK(dev_malloc(arena, &d, sizeof(T) * cap));
+}
+
 // ------------------------------------------------------------------------------------------------ profiling
 struct Env::ProfScope {
     Env &e; Env::ProfSlot *slot = nullptr; hipEvent_t a{}, b{}; hipStream_t s{};

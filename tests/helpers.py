@@ -815,6 +815,132 @@ def check_cycle_partial(lib, what):
             assert_same(want[k], g, "%s (batch of three, %s)" % (scs[k].name, what))
 
 
+def handover_scenarios():
+    """two plain battle worlds, 60 x 60 with 2 x 830 agents at hp 4 / damage 3 (kills in every step), whose population crosses the limits
+    between the engine's step drivers several times in 40 steps (HANDOVER_PLAN; the sizes at every step come from the oracle and are pinned
+    by check_driver_handovers): reinforcements at steps 12 and 30"""
+    rnd = lambda g, n: (g, "random", {"n": n})
+    more = lambda a, b: [("add", 0, "random", {"n": a}), ("add", 1, "random", {"n": b})]
+    return [Scenario("handover_%d" % k, "battle", 60, seed=6100 + 31 * k, place=[rnd(0, 830), rnd(1, 830)], steps=40, action_seed=400 + k,
+                     over={"small": {"hp": 4, "damage": 3}}, events={12: more(600, 600), 30: more(700, 700)}) for k in range(2)]
+
+
+# one environment's life across the drivers (play_handovers).  Steps 0 .. batch_from - 1 go call by call (Env::step_begin / step_end):
+#   0-4    above 1536 agents: the single-environment pipeline of plain games; clear_dead skipped behind step 1: step 2 meets stale events
+#          and does not fuse the rules
+#   5-11   deaths have brought the world below 1537: the one-launch step; clear_dead skipped behind step 7
+#   12     reinforcements: above 1536 again; group 0 is given actions twice in steps 13 and 16 -- the literal loop, at a size at which no
+#          one-launch step exists -- and clear_dead is skipped behind step 14
+#   23-39  deaths have brought it below 1537 again: env_cycle_many over the two worlds -- below batch_pipe_min (1537) the two-launch cycle,
+#          from the reinforcements of step 30 on the batched pipeline
+HANDOVER_PLAN = {"skip_clear": (1, 7, 14), "twice": (13, 16), "batch_from": 23}
+
+
+def play_handovers(lib, fused, counters_out=None):
+    """handover_scenarios by HANDOVER_PLAN on engine library `lib`; returns one trajectory per world.  Up to `batch_from` every world makes
+    the reference's calls one after the other (as run does); from there on `fused` sends both through ONE magent_amd.EnvBatch.cycle per step
+    (env_cycle_many), while a checker (fused=False) goes on alone through the reference call sequence (as run_cycle does).
+    counters_out receives, per step and world, (agents at the start of the step, engine_stats(), pipeline_stats()) read behind the step."""
+    scs, plan = handover_scenarios(), HANDOVER_PLAN
+    built = [sc.build(lib) for sc in scs]
+    envs, handles = [b[0] for b in built], [b[1] for b in built]
+    rss = [np.random.RandomState(sc.action_seed) for sc in scs]
+    again = [np.random.RandomState(sc.action_seed + 1000) for sc in scs]
+    if fused:
+        import torch
+        dev = torch_device(envs[0], lib)
+        batch = magent_amd.EnvBatch(envs, n_threads=1)
+        batch.order_streams = not is_emu(lib)
+    out = [[] for _ in scs]
+    for step in range(scs[0].steps):
+        recs, nums = [{} for _ in scs], []
+        for sc, env in zip(scs, envs):
+            sc.apply_events(env, step)
+        nums = [[env.get_num(h) for h in hs] for env, hs in zip(envs, handles)]
+        together = fused and step >= plan["batch_from"]
+        if together:
+            views = [[torch.empty((n,) + env.get_view_space(h), device=dev) for n, h in zip(ns, hs)] for env, hs, ns in zip(envs, handles, nums)]
+            feats = [[torch.empty((n,) + env.get_feature_space(h), device=dev) for n, h in zip(ns, hs)] for env, hs, ns in zip(envs, handles, nums)]
+            rews = [[torch.empty(n, device=dev) for n in ns] for ns in nums]
+            acts = [[torch.from_numpy(sc.draw(rs, env, g, h, ns[g])).to(dev) for g, h in enumerate(hs)] for sc, rs, env, hs, ns in zip(scs, rss, envs, handles, nums)]
+            for env, hs, rec in zip(envs, handles, recs):
+                for g, h in enumerate(hs):
+                    rec["id%d" % g] = env.get_agent_id(h)
+            device_sync(lib)
+            dones = batch.cycle(views, feats, acts, rews)
+            for k, (env, rec) in enumerate(zip(envs, recs)):
+                env.sync()
+                for g in range(len(handles[k])):
+                    rec["view%d" % g], rec["feat%d" % g], rec["reward%d" % g] = views[k][g].cpu().numpy(), feats[k][g].cpu().numpy(), rews[k][g].cpu().numpy()
+                rec["done"] = np.array([dones[k]], dtype=np.int32)
+        for k, (sc, env, hs, rec) in enumerate(zip(scs, envs, handles, recs)):
+            if not together:
+                for g, h in enumerate(hs):
+                    if nums[k][g] > 0:
+                        view, feat = env.get_observation(h)
+                        rec["view%d" % g], rec["feat%d" % g] = view.copy(), feat.copy()
+                    rec["id%d" % g] = env.get_agent_id(h)
+                    env.set_action(h, sc.draw(rss[k], env, g, h, nums[k][g]))
+                if step in plan["twice"]:       # (GridWorld.cc:403-454 appends: every agent of the group acts once per call)
+                    env.set_action(hs[0], sc.draw(again[k], env, 0, hs[0], nums[k][0]))
+                rec["done"] = np.array([env.step()], dtype=np.int32)
+                for g, h in enumerate(hs):
+                    rec["reward%d" % g] = env.get_reward(h)
+                    if step < plan["batch_from"]:       # (the state behind the step, the dead still listed)
+                        rec["alive_before%d" % g], rec["pos_before%d" % g] = env.get_alive(h).astype(np.uint8), env.get_pos(h)
+                if step not in plan["skip_clear"]:
+                    env.clear_dead()
+            for g, h in enumerate(hs):              # the state behind clear_dead
+                rec["num%d" % g] = np.array([env.get_num(h)], dtype=np.int32)
+                rec["pos%d" % g], rec["alive%d" % g], rec["ids_after%d" % g] = env.get_pos(h), env.get_alive(h).astype(np.uint8), env.get_agent_id(h)
+            out[k].append(rec)
+        if counters_out is not None:
+            counters_out.append([(sum(ns), env.engine_stats(), env.pipeline_stats()) for ns, env in zip(nums, envs)])
+    return out
+
+
+def check_driver_handovers(lib, what):
+    """play_handovers on engine library `lib` against the oracle driven alone, bit for bit -- and, from the engine's own counters (deltas of
+    pipeline_stats()[0], steps of the plain pipeline, and [6], cycles through the batched pipeline, step by step), which driver every step of
+    every world took: each driver must have run.  No counter tells the one-launch step from the literal loop: a step outside the plain
+    pipeline with a group given actions twice is the literal loop (Env::set_action_device), and steps 13 and 16 are such steps above 1536
+    agents, where no one-launch form exists; the others are the one-workgroup kernel (k_step_solo alone, the two-launch cycle in a batch).
+    MAGENT_TUNE attack_pairs=N fixes the optimistic rounds and thereby switches every one-workgroup form off (Env::solo_ok): under it those
+    steps go through the pipeline too and every such step is finished by the host, which is asserted instead."""
+    plan, fixed = HANDOVER_PLAN, "attack_pairs=" in os.environ.get("MAGENT_TUNE", "")
+    want = play_handovers(ensure_oracle(), fused=False)
+    for w in want:      # the plan's sizes, pinned on the oracle: above / below the limit of 1536 agents where the plan says so
+        sizes = [sum(len(r["id%d" % g]) for g in range(2)) for r in w]
+        assert len(w) == 40 and all(s > 1536 for s in sizes[0:5] + sizes[12:22] + sizes[30:40]) and all(s <= 1536 for s in sizes[5:12] + sizes[23:30]), sizes
+    counters = []
+    got = play_handovers(lib, fused=True, counters_out=counters)
+    for k, (w, g) in enumerate(zip(want, got)):
+        assert_same(w, g, "handover_%d (%s)" % (k, what))
+    for k in range(2):
+        took, plain, piped = [], 0, 0
+        for step, per_env in enumerate(counters):
+            total, _, ps = per_env[k]
+            d_plain, d_pipe = ps[0] - plain, ps[6] - piped
+            plain, piped = ps[0], ps[6]
+            assert d_plain in (0, 1) and d_pipe in (0, d_plain), (k, step, ps)
+            batch = step >= plan["batch_from"]
+            took.append("batched pipeline" if d_pipe else "pipeline" if d_plain else "literal loop" if step in plan["twice"] else
+                        "two-launch cycle" if batch else "one-launch step")
+            assert (d_plain == 1) == (step not in plan["twice"] and (total > 1536 or fixed)), (k, step, total, took)
+            assert d_pipe == (1 if batch and (total > 1536 or fixed) and (counters[step][1 - k][0] > 1536 or fixed) else 0), (k, step, total, took)
+        # behind a skipped clear_dead a step of the pipeline (rules not fused: stale events) and one of the one-launch step
+        assert took[2] == "pipeline" and took[15] == "pipeline" and took[8] == ("pipeline" if fixed else "one-launch step"), took
+        drivers = {"pipeline", "literal loop", "batched pipeline"} | (set() if fixed else {"one-launch step", "two-launch cycle"})
+        assert set(took) == drivers, (k, took)
+        es, ps = counters[-1][k][1], counters[-1][k][2]
+        if fixed and "attack_pairs=0" in os.environ["MAGENT_TUNE"]:
+            assert es[4] == ps[0] and es[5] == 0, (es, ps)       # the host finished every step of the pipeline
+        # the claim words are refilled for the first step of the pipeline and for the first one behind each literal loop (it leaves the scratch
+        # dirty), not behind one-workgroup steps (they keep it clean); no window of 63 epochs ends in under 63 such steps
+        assert ps[0] < 63 and ps[3] == 3, ps
+    return [c[2] for c in counters[-1]]
+
+
 def hash_rec(rec):
     """a step's record reduced to {key: xxh3-128 hex digest} as run_hashed does (the same digests as tests/golden/digests_fullsize.json)"""
     import xxhash

@@ -239,6 +239,23 @@ def test_emulated_fuzz_batched_pipeline_with_groups_left_out(emu):
         assert out.returncode == 0 and "%d seeds, 0 failures" % n in out.stdout and "batched pipeline (pipe.hip): %d " % n in out.stdout, (tune, out.stdout[-3000:], out.stderr[-2000:])
 
 
+@pytest.mark.parametrize("leg", ["default", "scrambled", "host_finishes"])
+def test_driver_handovers(emu, leg):
+    """one environment's life across the step drivers (helpers.HANDOVER_PLAN): the single-environment pipeline, the one-launch step once deaths
+    bring the world below 1537 agents, steps behind a skipped clear_dead (stale events: rules not fused), steps with a group given actions
+    twice (the literal loop), reinforcements that lift it over the limit again, then env_cycle_many as one of a batch of two such worlds --
+    the two-launch cycle below batch_pipe_min, the batched pipeline above -- every output of every step against the oracle driven alone
+    through the reference call sequence; which driver every step took is asserted from the engine's own counters
+    (helpers.check_driver_handovers).  What one driver leaves for the next -- the per-cell scratch, the device tables, k_strike's survivor
+    counts, the stale events, the minimap made ahead -- is what the drivers' shared host bookkeeping keeps."""
+    code = ("import os, sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import helpers as H\n"
+            "print('ok', H.check_driver_handovers(H.ensure_emu(), 'hipemu'))\n") % (ROOT, os.path.join(ROOT, "tests"))
+    extra = {"default": {}, "scrambled": {"HIPEMU_SCRAMBLE": "7"}, "host_finishes": {"MAGENT_TUNE": "attack_pairs=0"}}[leg]
+    p = subprocess.run([sys.executable, "-c", code], env=H.merge_env(os.environ, {"OMP_NUM_THREADS": "1"}, extra), capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "ok" in p.stdout, (leg, p.stdout[-1500:] + p.stderr[-3000:])
+
+
 @pytest.mark.parametrize("env,needle", [({"MAGENT_SOLO_STEP": "0"}, "MAGENT_TUNE=solo_step="), ({"MAGENT_RENDER_PAD": "1"}, "has no successor"),
                                         ({"MAGENT_TUNE": "solo_stepp=0"}, "unknown entry")],
                          ids=["removed_variable_with_successor", "removed_variable_without", "unknown_tune_key"])

@@ -120,6 +120,22 @@ def test_batched_pipeline_with_groups_left_out_variants(tune):
     assert p.returncode == 0 and "ok" in p.stdout, (tune, p.stdout[-1500:] + p.stderr[-3000:])
 
 
+@pytest.mark.parametrize("tune", ["", "attack_pairs=0"], ids=["default", "host_finishes"])
+def test_driver_handovers(tune):
+    """one environment's life across the step drivers (helpers.HANDOVER_PLAN; tests/test_emu_parity.py::test_driver_handovers): pipeline,
+    one-launch step, skipped clear_dead, the literal loop, reinforcements, then the two-launch cycle and the batched pipeline as one of a
+    batch of two -- bit for bit against the oracle driven alone, the driver of every step asserted from the engine's own counters; with the
+    defaults and with the host finishing every step of the pipeline (the engine reads MAGENT_TUNE once: a process each)"""
+    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "import torch, helpers as H\n"
+            "print('ok', H.check_driver_handovers(H.HIP_LIB, 'MI355X'))\n") % (H.ROOT, os.path.join(H.ROOT, "tests"))
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k != "MAGENT_TUNE"}
+    p = subprocess.run([sys.executable, "-c", code], env=H.merge_env(env, {"OMP_NUM_THREADS": "1"}, {"MAGENT_TUNE": tune} if tune else {}), capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "ok" in p.stdout, (tune, p.stdout[-1500:] + p.stderr[-3000:])
+
+
 def test_batched_pipeline_over_a_long_episode(oracle):
     """the batched pipeline over what only acts with the length of an episode (the claim words' epoch window, refilled every 63 steps by every
     environment of the batch for itself; the carried round stamps; the batch's budget of optimistic rounds: three, four while some environment's is raised):
