@@ -6,6 +6,9 @@
  * GridWorld.get_observation and GridWorld.set_action -- BASELINE config 5's policy step.  Additive: the reference has no
  * C entry point here (its model is a TensorFlow graph); the Python binding is magent_amd/builtin/torch_model/hip_policy.py.
  *
+ * Further down: the same network in float32, the deep recurrent Q network's acting step in float32 and with bf16 operands
+ * (policy_drqn_infer_f32, policy_drqn_infer), and the actor-critic's.
+ *
  * All pointers are DEVICE pointers; the call enqueues two kernels on `stream` and returns.  Inputs are the engine's own
  * observation tensors (env_get_observation_device): view float[n][view_h][view_w][view_c], feature float[n][feat].
  * Numerics: inputs, weights and inter-layer activations are rounded to bf16, products accumulate in f32 (MFMA).
@@ -119,6 +122,46 @@ int policy_drqn_f32_workspace_bytes(const PolicyDqnShape *shape, int n, size_t *
 int policy_drqn_infer_f32(const PolicyDqnShape *shape, const PolicyDrqnWeightsF32 *weights, const float *view, const float *feature, int n,
                           const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
                           void *workspace, int *actions, float *q, void *stream);
+
+/* ---- the same recurrent network with bf16 matrix operands (v_mfma_f32_32x32x16_bf16) -- magent_amd/csrc/policy_drqn_bf16.hip: an opt-in,
+ * as policy_dqn_infer is beside policy_dqn_infer_f32.  The trunk is the bf16 DQN's (k_dqn_conv, then k_dqn_head stopped after its hidden
+ * layer); it leaves x = relu(dense_view) || relu(dense_emb) as bf16[n][512] in the workspace, in hidden SLOT order (value 32 T' + s of a
+ * row is hidden unit 32 T' + slot s's output, T' = 0..15: the order PolicyDqnWeights' head reads).
+ * Rounded to bf16 (nearest even): the views, the features, every weight matrix, conv1's bias, the conv outputs, the two hidden halves,
+ * h as the GRU's operand and h' as the head's operand.  Everything else is float32: accumulation, the other biases, the gates and the
+ * blend h' = (1 - z) n + z h, which takes the UNROUNDED h.  The state table is the f32 entry's, float[.][512]: the two paths can hand
+ * their states to each other, and bf16 error does not compound through the blend.
+ * Weights in (bf16) fragment order:
+ *   gru  : torch's weight_ih_l0 and weight_hh_l0 [3 x 512][512] (gates r, z, n) side by side; K = x's 512 hidden SLOTS (weight_ih_l0's
+ *          columns permuted: column 32 T' + s is the weight of unit 32 T' + (s & 3) + 8 ((s & 15) >> 2) + 4 (s >> 4)), then h's 512 units in
+ *          natural order; the three gate tiles of hidden tile T are adjacent: k-step s, tile T, gate G at [s][3 T + G]; outputs (hidden
+ *          units) in natural order                                                                                       [64][48][64][8]
+ *   head : K = the 512 state units, natural order; outputs as for PolicyDrqnWeightsF32's head                           [32][64][8]
+ * gru_bias, gru_bias0, head_bias: float, as for PolicyDrqnWeightsF32 (gru_bias0's NaN marks a row of the bf16-ROUNDED weight_hh_l0 that is
+ * not finite) */
+typedef struct {
+    PolicyDqnWeights trunk;       /* conv1 .. dense_emb and their biases as for policy_dqn_infer; trunk.head and trunk.value_bias are not read */
+    const void *gru;
+    const float *gru_bias, *gru_bias0;
+    const void *head;
+    const float *head_bias;
+    int dueling;
+} PolicyDrqnWeights;
+
+/* 1 if the bf16 DRQN kernels take this shape: policy_dqn_supported's region */
+int policy_drqn_supported(const PolicyDqnShape *shape);
+/* size of the workspace of one call with n agents (the trunk's activations, then x bf16[n][512]) */
+int policy_drqn_workspace_bytes(const PolicyDqnShape *shape, int n, size_t *bytes);
+/* One step of n agents: the arguments, the state table's look-up (the last equal entry; an absent id starts from zeros; count == 0 takes
+ * gru_bias0), the alignment rule (states, new_states, workspace: 16 bytes), the actions' order and the return codes of
+ * policy_drqn_infer_f32.  Four kernels on `stream`; a refused call has written nothing. */
+int policy_drqn_infer(const PolicyDqnShape *shape, const PolicyDrqnWeights *weights, const float *view, const float *feature, int n,
+                      const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
+                      void *workspace, int *actions, float *q, void *stream);
+/* the same with the views as the engine's bf16 cells ([n][view_h][view_w][8], channel 7 = 1.0; 16-byte aligned), as policy_dqn_infer_bf16 */
+int policy_drqn_infer_bf16(const PolicyDqnShape *shape, const PolicyDrqnWeights *weights, const void *view_cells, const float *feature, int n,
+                           const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
+                           void *workspace, int *actions, float *q, void *stream);
 
 /* ---- one acting step of the advantage actor-critic (magent_amd/builtin/torch_model/a2c.py: _ActorCritic.forward, then the action draw)
  * in float32 -- magent_amd/csrc/policy_a2c_f32.hip.  No convolution: the flattened view (K = view_h * view_w * view_c values, in the

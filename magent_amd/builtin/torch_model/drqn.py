@@ -51,7 +51,7 @@ class _RecurrentQNet(nn.Module):
 class DeepRecurrentQNetwork(BaseModel):
     def __init__(self, env, handle, name, batch_size=32, unroll_step=8, reward_decay=0.99, learning_rate=1e-4, train_freq=1,
                  memory_size=20000, target_update=2000, eval_obs=None, use_dueling=True, use_double=True,
-                 use_episode_train=False, custom_view_space=None, custom_feature_space=None, device=None):
+                 use_episode_train=False, custom_view_space=None, custom_feature_space=None, device=None, infer_dtype=None):
         BaseModel.__init__(self, env, handle)
         self.env, self.handle, self.name, self.subclass_name = env, handle, name, "torchdrqn"
         self.view_space = tuple(custom_view_space or env.get_view_space(handle))
@@ -72,13 +72,26 @@ class DeepRecurrentQNetwork(BaseModel):
         # Acting on device-resident float32 observations goes through hand-written kernels (magent_amd/csrc/policy_drqn_f32.hip: the DQN's
         # trunk, a GRU(512) cell, the head) with the GRU states in a device table keyed by agent id; MAGENT_POLICY_F32=torch keeps the
         # PyTorch forward pass below, as for the DQN.  Numpy inputs, CPU devices and shapes the kernels do not take use that path too.
-        self._hip = None
-        if self.device.type == "cuda" and os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
-            try:
-                from .hip_policy import HipDrqnPolicyF32
-                self._hip = HipDrqnPolicyF32(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
-            except (ValueError, OSError, AttributeError):
-                self._hip = None
+        # infer_dtype "bf16" (the argument, or MAGENT_POLICY_DTYPE=bf16 for scripts run unmodified) is the DQN's opt-in: acting then goes
+        # through the bf16 MFMA kernels (magent_amd/csrc/policy_drqn_bf16.hip: bf16 matrix operands, float32 accumulation, gates, blend and
+        # states) where the shape is theirs, and through what "f32" would use where it is not.  `bf16_kernels` says which.  Training is
+        # untouched by it.
+        self.infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
+        if self.infer_dtype not in ("f32", "bf16"):
+            raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (self.infer_dtype,))
+        self._hip, self.bf16_kernels = None, False
+        if self.device.type == "cuda":
+            from . import hip_policy
+            kinds = [hip_policy.HipDrqnPolicy] if self.infer_dtype == "bf16" else []
+            if os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
+                kinds.append(hip_policy.HipDrqnPolicyF32)
+            for kind in kinds:
+                try:
+                    self._hip = kind(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
+                    self.bf16_kernels = kind is hip_policy.HipDrqnPolicy
+                    break
+                except (ValueError, OSError, AttributeError):
+                    self._hip = None
         # episodes: (views, features, actions, rewards, terminals) as device tensors; the oldest fall out (drqn.py:129-131)
         self.memory_size = memory_size
         self.replay_buffer = collections.deque(maxlen=memory_size)
@@ -102,9 +115,13 @@ class DeepRecurrentQNetwork(BaseModel):
         self._agent_states = dict(mapping)
 
     def _on_kernels(self, view, feature, n):
-        return (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
-                and feature.device == view.device and view.dtype == torch.float32 and feature.dtype == torch.float32 and view.is_contiguous()
-                and feature.is_contiguous() and tuple(view.shape) == (n,) + self.view_space and tuple(feature.shape) == (n,) + self.feature_space)
+        if not (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
+                and feature.device == view.device and feature.dtype == torch.float32 and view.is_contiguous() and feature.is_contiguous()
+                and tuple(feature.shape) == (n,) + self.feature_space):
+            return False
+        if view.dtype == torch.bfloat16:     # the engine's bf16 cells [n, H, W, 8]: the bf16 kernels' operands as they are
+            return self.bf16_kernels and tuple(view.shape) == (n,) + self.view_space[:2] + (8,)
+        return view.dtype == torch.float32 and tuple(view.shape) == (n,) + self.view_space
 
     @torch.no_grad()
     def infer_action(self, raw_obs, ids, policy="e_greedy", eps=0):
@@ -121,6 +138,11 @@ class DeepRecurrentQNetwork(BaseModel):
             ids_dev = ids.to(view.device, torch.int32) if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids, dtype=np.int32)).to(view.device)
             best = self._hip.infer(view, feature, ids_dev)
         else:
+            if isinstance(view, torch.Tensor) and view.dtype == torch.bfloat16:
+                # bf16 cells [n, H, W, 8] (channels, zeros, a constant 1) without the bf16 kernels: the channels go back to float32
+                view = view[..., :self.view_space[-1]].float()
+                if self._on_kernels(view, feature, n):
+                    return self.infer_action((view.contiguous(), feature), ids, policy, eps)
             ids_host = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
             zero = torch.zeros(_RecurrentQNet.STATE, device=self.device)
             prev = self.agent_states

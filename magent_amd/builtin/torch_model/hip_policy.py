@@ -1,5 +1,6 @@
 """Binding of the hand-written MI355X inference kernels for the reference's deep Q network (include/magent_policy.h,
-magent_amd/csrc/policy.hip) to the PyTorch model that owns the parameters (dqn.py: _QNet).
+magent_amd/csrc/policy.hip) to the PyTorch model that owns the parameters (dqn.py: _QNet) -- and, further down, of the float32 kernels,
+the recurrent network's (float32 and bf16: one state table, _DrqnPolicy) and the actor-critic's.
 
 The kernels want every weight matrix in the operand order of v_mfma_f32_32x32x16_bf16 ("fragment order") and every
 activation in the order a lane of the MFMA result holds its 16 outputs ("slot order"); both are plain index permutations of
@@ -133,6 +134,31 @@ def _pad_k(w, k):
     return torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], dim=1) if w.shape[1] < k else w
 
 
+def _trunk_bf16(q, shape, dev):
+    """conv1, conv2, dense_view, dense_emb of a _QNet / _RecurrentQNet (the same trunk) in bf16 fragment order with their biases in slot
+    order, and `hidden`: the hidden unit held in each of the 512 hidden slots (the order the kernels keep the hidden layer in)"""
+    ch = slot_channels(dev)
+    c = shape.view_c
+    k_dense = (shape.view_h - 4) * (shape.view_w - 4) * 32
+    w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
+    w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
+    w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
+    # the kernel pairs the taps (0|3) (1|4) (2|5) (6|7) (8|pad) into its five k-steps (policy.hip: k_dqn_conv)
+    w1 = _pad_k(w1.reshape(32, 72), 80).reshape(32, 10, 8)[:, CONV1_TAP_ORDER].reshape(32, 80)
+    w2 = q.conv2.weight.detach().float()[:, ch].permute(0, 2, 3, 1).reshape(32, 288)            # K = tap * 32 + slot
+    wv = q.dense_view.weight.detach().float().reshape(256, -1, 32)[:, :, ch].reshape(256, k_dense)   # K = position * 32 + slot
+    fk = (shape.feat + 15) // 16 * 16
+    we = _pad_k(q.dense_emb.weight.detach().float(), fk)
+    hidden = (torch.arange(16, device=dev)[:, None] * 32 + ch[None, :]).reshape(512)              # hidden slot -> hidden unit
+    return {
+        "conv1": fragment_order(w1), "conv2": fragment_order(w2), "dense_view": fragment_order(wv),
+        "dense_emb": fragment_order(we),
+        "conv2_bias": q.conv2.bias.detach().float()[ch].contiguous(),
+        "dense_view_bias": q.dense_view.bias.detach().float()[hidden[:256]].contiguous(),
+        "dense_emb_bias": q.dense_emb.bias.detach().float()[hidden[:256]].contiguous(),
+    }, hidden
+
+
 class HipDqnPolicy(_Packed):
     """greedy actions (and, for tests, the Q values) of a dueling conv _QNet, computed by k_dqn_conv + k_dqn_head"""
 
@@ -146,26 +172,9 @@ class HipDqnPolicy(_Packed):
     def pack(self):
         q, dev = self.qnet, self.device
         stamp = _SourceStamp(q)
-        ch = slot_channels(dev)
-        c = self.shape.view_c
-        w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
-        w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
-        w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
-        # the kernel pairs the taps (0|3) (1|4) (2|5) (6|7) (8|pad) into its five k-steps (policy.hip: k_dqn_conv)
-        w1 = _pad_k(w1.reshape(32, 72), 80).reshape(32, 10, 8)[:, CONV1_TAP_ORDER].reshape(32, 80)
-        w2 = q.conv2.weight.detach().float()[:, ch].permute(0, 2, 3, 1).reshape(32, 288)            # K = tap * 32 + slot
-        wv = q.dense_view.weight.detach().float().reshape(256, -1, 32)[:, :, ch].reshape(256, self.k_dense)   # K = position * 32 + slot
-        fk = (self.shape.feat + 15) // 16 * 16
-        we = _pad_k(q.dense_emb.weight.detach().float(), fk)
-        hidden = (torch.arange(16, device=dev)[:, None] * 32 + ch[None, :]).reshape(512)              # hidden slot -> hidden unit
+        t, hidden = _trunk_bf16(q, self.shape, dev)
         head, _ = _head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], dev)
-        t = {
-            "conv1": fragment_order(w1), "conv2": fragment_order(w2), "dense_view": fragment_order(wv),
-            "dense_emb": fragment_order(we), "head": fragment_order(head[:, hidden]),
-            "conv2_bias": q.conv2.bias.detach().float()[ch].contiguous(),
-            "dense_view_bias": q.dense_view.bias.detach().float()[hidden[:256]].contiguous(),
-            "dense_emb_bias": q.dense_emb.bias.detach().float()[hidden[:256]].contiguous(),
-        }
+        t["head"] = fragment_order(head[:, hidden])
         w = _Weights()
         _set_pointers(w, t)
         w.value_bias = float(q.value.bias.detach().float().item())
@@ -266,19 +275,22 @@ class _DrqnWeights(ctypes.Structure):
                 ("head", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("dueling", ctypes.c_int)]
 
 
-class HipDrqnPolicyF32(_Packed):
-    """one acting step of a _RecurrentQNet in float32 -- the DQN's trunk (k_dqn_conv_f32 + k_dqn_head_f32), a GRU(512) cell (k_drqn_gru_f32),
-    the head and argmax (k_drqn_head_f32): magent_amd/csrc/policy_drqn_f32.hip -- and the GRU state of every agent id in device memory.
+class _DrqnPolicy(_Packed):
+    """what the two DRQN policies share: the GRU state of every agent id in device memory, the packing of the GRU and the head around a
+    trunk, and the chunked step.  A subclass names its entries of the library (`_abi`: supported, workspace_bytes) and gives pack() / infer().
 
-    The state table is the last call's output: its ids in call order, their states (row k: the k-th id's), and for the next call's lookup
-    the ids sorted stably with their rows.  An id of the next call takes the state of its last occurrence in the table, any other id
-    starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  `lib`: _Packed."""
+    The state table is the last call's output: its ids in call order, their states float32 [.][512] (row k: the k-th id's), and for the
+    next call's lookup the ids sorted stably with their rows.  An id of the next call takes the state of its last occurrence in the table,
+    any other id starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  Both kernel paths keep this
+    one format: a table can be handed from one to the other (states_dict / load_states).  `lib`: _Packed."""
     STATE = 512
+    _abi = None
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072, lib=None):
         super().__init__(qnet, view_space, feature_space, n_action, device, chunk, lib)
-        if qnet.rnn.hidden_size != self.STATE or not self._lib.policy_drqn_f32_supported(ctypes.byref(self.shape)):
-            raise ValueError("network shape not taken by the HIP f32 DRQN kernels")
+        supported = getattr(self._lib, self._abi[0])          # (AttributeError: a library without these kernels)
+        if qnet.rnn.hidden_size != self.STATE or not supported(ctypes.byref(self.shape)):
+            raise ValueError("network shape not taken by the HIP DRQN kernels (%s)" % self._abi[0])
         self.clear()
 
     # ---- the state table
@@ -306,26 +318,29 @@ class HipDrqnPolicyF32(_Packed):
         self._set_table(ids, states)
 
     # ---- weights
-    @torch.no_grad()
-    def pack(self):
+    def _pack_recurrent(self, t, stamp, frag, x_order=None, round_to=None):
+        """the GRU and the head into `t` (a packed trunk) and the whole into the library's struct.  frag: the fragment order of the matrix
+        operands; x_order: the hidden unit in each position of the trunk's x (None: natural order); round_to: the operands' dtype, for
+        gru_bias0 (a weight that is finite in float32 can round to Inf)"""
         q, dev, S, A = self.qnet, self.device, self.STATE, self.shape.n_action
-        stamp = _SourceStamp(q)
-        t = _trunk_f32(q, self.shape, dev)
         rnn = q.rnn
         wih, whh = rnn.weight_ih_l0.detach().float(), rnn.weight_hh_l0.detach().float()        # [3 S][S], gates r, z, n
         bih, bhh = rnn.bias_ih_l0.detach().float(), rnn.bias_hh_l0.detach().float()
+        if x_order is not None:
+            wih = wih[:, x_order]
         wcat = torch.cat([wih, whh], dim=1).reshape(3, S // 32, 32, 2 * S).permute(1, 0, 2, 3).reshape(3 * S, 2 * S)   # tile 3 T + gate
-        t["gru"] = fragment_order_f32(wcat)
+        t["gru"] = frag(wcat)
         bias = lambda bh: torch.stack([bih[:S] + bh[:S], bih[S:2 * S] + bh[S:2 * S], bih[2 * S:], bh[2 * S:]]).contiguous()
         t["gru_bias"] = bias(bhh)
-        # a zero state: W_h 0 is 0, or NaN where a row of W_h is not finite (torch's W_h @ 0)
-        w0 = torch.where(torch.isfinite(whh).all(dim=1), torch.zeros_like(bhh), torch.full_like(bhh, float("nan")))
+        # a zero state: W_h 0 is 0, or NaN where a row of W_h (as the kernels hold it) is not finite (torch's W_h @ 0)
+        held = whh if round_to is None else whh.to(round_to).float()
+        w0 = torch.where(torch.isfinite(held).all(dim=1), torch.zeros_like(bhh), torch.full_like(bhh, float("nan")))
         t["gru_bias0"] = bias(bhh + w0)
         if q.use_dueling:
             head, hb = _head_32x512([(0, q.advantage.weight), (A, q.value.weight)], dev, [(A, q.value.bias)])
         else:
             head, hb = _head_32x512([(0, q.value.weight)], dev, [(0, q.value.bias)])
-        t["head"], t["head_bias"] = fragment_order_f32(head), hb
+        t["head"], t["head_bias"] = frag(head), hb
         w = _DrqnWeights()
         _set_pointers(w.trunk, t, ("conv1", "conv2", "dense_view", "dense_emb", "conv2_bias", "dense_view_bias", "dense_emb_bias"))
         _set_pointers(w, t, ("gru", "gru_bias", "gru_bias0", "head", "head_bias"))
@@ -333,13 +348,12 @@ class HipDrqnPolicyF32(_Packed):
         self._set_packed(t, w, stamp)
 
     # ---- one step
-    @torch.no_grad()
-    def infer(self, view, feature, ids, want_q=False):
-        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.
-        Enqueues the step on torch's current stream and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+    def _step(self, entry, view, feature, ids, want_q):
+        """the library's `entry` on every chunk of the call (all chunks read the same previous table), then the new table"""
         assert view.device == feature.device == ids.device and view.device.type == self.device.type
-        assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
-        assert view.shape[-1] == self.shape.view_c and ids.dtype == torch.int32 and view.shape[0] == feature.shape[0] == ids.shape[0]
+        assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32
+        assert ids.dtype == torch.int32 and view.shape[0] == feature.shape[0] == ids.shape[0]
+        call = getattr(self._lib, entry)
         if self.stale():
             self.pack()
         n, dev = view.shape[0], view.device
@@ -347,16 +361,57 @@ class HipDrqnPolicyF32(_Packed):
         actions = torch.empty(n, dtype=torch.int32, device=dev)
         q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=dev) if want_q else None
         new_states = torch.empty((n, self.STATE), dtype=torch.float32, device=dev)
-        self._grow_work(dev, self._lib.policy_drqn_f32_workspace_bytes, min(n, self.chunk))
+        self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, self.chunk))
         stream = _stream(dev)
         count = int(self._sorted.numel())
         table = (self._sorted.data_ptr(), self._rows.data_ptr(), self._states.data_ptr()) if count else (None, None, None)
-        self._chunked("policy_drqn_infer_f32", n, self.chunk, lambda beg, m: self._lib.policy_drqn_infer_f32(
+        self._chunked(entry, n, self.chunk, lambda beg, m: call(
             ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, ids[beg:].data_ptr(),
             table[0], table[1], table[2], count, new_states[beg:].data_ptr(), self._work.data_ptr(), actions[beg:].data_ptr(),
             _ptr(q[beg:] if want_q else None), stream))
         self._set_table(ids, new_states)
         return (actions, q) if want_q else actions
+
+
+class HipDrqnPolicyF32(_DrqnPolicy):
+    """one acting step of a _RecurrentQNet in float32 -- the DQN's trunk (k_dqn_conv_f32 + k_dqn_head_f32), a GRU(512) cell (k_drqn_gru_f32),
+    the head and argmax (k_drqn_head_f32): magent_amd/csrc/policy_drqn_f32.hip -- and the GRU state of every agent id in device memory
+    (_DrqnPolicy)."""
+    _abi = ("policy_drqn_f32_supported", "policy_drqn_f32_workspace_bytes")
+
+    @torch.no_grad()
+    def pack(self):
+        stamp = _SourceStamp(self.qnet)
+        self._pack_recurrent(_trunk_f32(self.qnet, self.shape, self.device), stamp, fragment_order_f32)
+
+    @torch.no_grad()
+    def infer(self, view, feature, ids, want_q=False):
+        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.
+        Enqueues the step on torch's current stream and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+        assert view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c
+        return self._step("policy_drqn_infer_f32", view, feature, ids, want_q)
+
+
+class HipDrqnPolicy(_DrqnPolicy):
+    """one acting step of a _RecurrentQNet with bf16 matrix operands -- the bf16 DQN's trunk (k_dqn_conv + k_dqn_head stopped after the
+    hidden layer), the GRU cell (k_drqn_gru_bf16), the head and argmax (k_drqn_head_bf16): magent_amd/csrc/policy_drqn_bf16.hip.  Gates,
+    blend and the state table are float32 (_DrqnPolicy): the rounding points are listed in include/magent_policy.h."""
+    _abi = ("policy_drqn_supported", "policy_drqn_workspace_bytes")
+
+    @torch.no_grad()
+    def pack(self):
+        stamp = _SourceStamp(self.qnet)
+        t, hidden = _trunk_bf16(self.qnet, self.shape, self.device)
+        self._pack_recurrent(t, stamp, fragment_order, x_order=hidden, round_to=torch.bfloat16)
+
+    @torch.no_grad()
+    def infer(self, view, feature, ids, want_q=False):
+        """view float32 [n][H][W][C] -- or bfloat16 [n][H][W][8], the engine's cells (GridWorld.get_observation_device_bf16) --, feature
+        float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.  Enqueues the step on torch's current stream
+        and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+        cells16 = view.dtype == torch.bfloat16
+        assert (cells16 and view.shape[-1] == 8) or (view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c)
+        return self._step("policy_drqn_infer_bf16" if cells16 else "policy_drqn_infer", view, feature, ids, want_q)
 
 
 # ---------------------------------------------------------------------------------------------------- the actor-critic (a2c.py)

@@ -66,6 +66,10 @@ POLICY_ABI = [
     ("policy_drqn_f32_supported", [_vp]),
     ("policy_drqn_f32_workspace_bytes", [_vp, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_drqn_infer_f32", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("policy_drqn_supported", [_vp]),
+    ("policy_drqn_workspace_bytes", [_vp, _i, _c.POINTER(_c.c_size_t)]),
+    ("policy_drqn_infer", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("policy_drqn_infer_bf16", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     ("policy_a2c_f32_supported", [_vp]),
     ("policy_a2c_f32_workspace_bytes", [_vp, _i, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_a2c_infer_f32", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

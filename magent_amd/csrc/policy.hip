@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "../../include/magent_policy.h"
+#include "policy_bf16_dev.h"
 #include "policy_host.h"
 #include "tune.h"
 
@@ -325,6 +326,7 @@ struct HeadArgs {
     int *actions;             // [n] argmax_a Q
     float *q;                 // [n][n_action] or null
     long long *stamps;        // STAMPS instantiation: per workgroup, the cycle counter at the phase boundaries
+    bf16x8 *xout;             // HIDDEN_OUT instantiation: x [n][512] bf16, the hidden layer in slot order (policy_bf16_dev.h); wh is not read
 };
 
 // one half of the hidden layer (256 values: relu(dense_view), later relu(dense_emb)) of the 128 agents: [agent][32 chunks of
@@ -338,7 +340,9 @@ __device__ __forceinline__ int hid_at(int agent, int chunk) { return agent * 32 
 // K-chunks ahead; a chunk is 0.26 us of MFMA work per wave.
 // (History per 131072 agents, 64 agents / 4 waves per workgroup: operands loaded at the k-step that uses them 0.45 ms, 79 % of
 // the wave cycles waiting; one chunk ahead 0.31 ms -- two weight fragments per k-step left room for one chunk of look-ahead only.)
-template <bool STAMPS>
+// HIDDEN_OUT (the DRQN's trunk, policy_drqn_bf16.hip): the kernel stops after the two hidden halves and stores them, as they stand in
+// s_hid, as x [n][512] bf16 -- half h, chunk c of an agent at 16-byte unit 32 h + c of its 1 KB row: hidden SLOT order.
+template <bool STAMPS, bool HIDDEN_OUT = false>
 __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
     const long long t_begin = STAMPS ? clock64() : 0;
     extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
@@ -384,8 +388,10 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
     // what the phases behind the main loop need from L2 is fetched now (measured: loaded at their point of use -- 32 dependent
     // round trips for the head's weights alone -- those phases were 100 of the kernel's 280 us): the head's weights and the biases of
     // both hidden halves go to LDS (the biases sat in 32 registers through the main loop in round 2; the activation ring has them now)
+    if (!HIDDEN_OUT) {
 #pragma unroll
-    for (int k = 0; k < 4; k++) s_wh[k * HEAD_THREADS + tid] = A.wh[k * HEAD_THREADS + tid];
+        for (int k = 0; k < 4; k++) s_wh[k * HEAD_THREADS + tid] = A.wh[k * HEAD_THREADS + tid];
+    }
     float *s_bias = (float *)(s_wh + 32 * 64);            // [2][8 tiles][2][16]
     s_bias[tid] = tid < 256 ? A.bv[tid] : A.be[tid - 256];
 
@@ -485,6 +491,15 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
 #pragma unroll
             for (int e = 0; e < 8; e++) fv[i][e] = frow[min((spiece + 4 * i) * 8 + e, A.F - 1)];       // (clamped: selected below)
     }
+    // HIDDEN_OUT: one half of the hidden layer, s_hid -> x.  Unit u = 512 k + tid: agent u >> 5, chunk u & 31 -- 32 consecutive lanes
+    // store one agent's 512 bytes
+    auto x_out = [&](int half) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const int u = k * HEAD_THREADS + tid, agent = u >> 5, c = u & 31;
+            if (a0 + agent < A.n) A.xout[(size_t)(a0 + agent) * 64 + half * 32 + c] = s_hid[hid_at(agent, c)];
+        }
+    };
     hidden_out(0);
     // ---- the dueling head: [32 outputs] x [128 agents], K = 512 hidden slots in two halves; waves 0..3 take 32 agents each
     f32x16 h = {0};
@@ -499,7 +514,8 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
         for (int e = 0; e < 8; e++) v[e] = (__bf16)(c * 8 + e < A.F ? fv[i][e] : 0.0f);
         if (c < A.FK / 8) s_act[sdst + (c ^ ssw)] = v;
     }
-    if (w < 4) {
+    if (HIDDEN_OUT) x_out(0);
+    else if (w < 4) {
 #pragma unroll 4
         for (int s = 0; s < 16; s++) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s_wh[s * 64 + l], s_hid[hid_at(hagent, 2 * s + g)], h, 0, 0, 0);
     }
@@ -517,7 +533,8 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
     __syncthreads();     // the first half of the head has read relu(dense_view)
     hidden_out(1);
     __syncthreads();
-    if (w < 4) {
+    if (HIDDEN_OUT) x_out(1);
+    else if (w < 4) {
 #pragma unroll 4
         for (int s = 16; s < 32; s++) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s_wh[s * 64 + l], s_hid[hid_at(hagent, 2 * (s - 16) + g)], h, 0, 0, 0);
         const int agent = hagent;
@@ -576,8 +593,9 @@ int policy_dqn_supported(const PolicyDqnShape *s) {
            s->n_action >= 1 && s->n_action <= 31;
 }
 
+// x == nullptr: the DQN (actions, q).  x != nullptr: the trunk alone -- k_dqn_head<., true> stores the hidden layer there
 static int dqn_infer(const PolicyDqnShape *s, const PolicyDqnWeights *w, const void *view_any, bool cells16, const float *feat, int n,
-                     void *act_workspace, int *actions, float *q, void *stream) {
+                     void *act_workspace, int *actions, float *q, void *stream, void *x = nullptr) {
     const float *view = (const float *)view_any;
     if (!policy_dqn_supported(s)) return 1;
     if (n <= 0) return 0;
@@ -599,6 +617,7 @@ static int dqn_infer(const PolicyDqnShape *s, const PolicyDqnWeights *w, const v
                                          {reinterpret_cast<const void *>(k_dqn_conv<true, true>), 150 * 1024},
                                          {reinterpret_cast<const void *>(k_dqn_conv<true, true, true>), 150 * 1024},
                                          {reinterpret_cast<const void *>(k_dqn_head<false>), (int)HEAD_LDS},
+                                         {reinterpret_cast<const void *>(k_dqn_head<false, true>), (int)HEAD_LDS},
                                          {reinterpret_cast<const void *>(k_dqn_head<true>), (int)HEAD_LDS}})) return 2;
     ConvArgs C{};
     C.view = view; C.act = (__bf16 *)act_workspace; C.w1 = (const bf16x8 *)w->conv1; C.w2 = (const bf16x8 *)w->conv2; C.b2 = w->conv2_bias;
@@ -608,7 +627,8 @@ static int dqn_infer(const PolicyDqnShape *s, const PolicyDqnWeights *w, const v
     // development (MAGENT_TUNE policy_stamps=1, bf16-cell views of the battle shape only): wave 0 of every workgroup reads the cycle counter at
     // its phase boundaries; the launch is waited for and the averages go to stderr.  A separate instantiation: the product kernels
     // carry none of it.
-    static const bool stamps_on = magent_amd::tune("policy_stamps", 0) != 0;
+    static const bool stamps_tuned = magent_amd::tune("policy_stamps", 0) != 0;
+    const bool stamps_on = stamps_tuned && !x;
     const int head_grid = (n + HEAD_M - 1) / HEAD_M;
     long long *d_stamps = nullptr;
     const bool stamp_conv = stamps_on && cells16 && f13;
@@ -625,8 +645,9 @@ static int dqn_infer(const PolicyDqnShape *s, const PolicyDqnWeights *w, const v
     HeadArgs Hd{};
     Hd.act = (const __bf16 *)act_workspace; Hd.feat = feat; Hd.wv = (const bf16x8 *)w->dense_view; Hd.we = (const bf16x8 *)w->dense_emb; Hd.wh = (const bf16x8 *)w->head;
     Hd.bv = w->dense_view_bias; Hd.be = w->dense_emb_bias; Hd.value_bias = w->value_bias;
-    Hd.n = n; Hd.K = H2 * W2 * 32; Hd.F = s->feat; Hd.FK = (s->feat + 15) / 16 * 16; Hd.n_action = s->n_action; Hd.actions = actions; Hd.q = q;
-    if (stamps_on) {
+    Hd.n = n; Hd.K = H2 * W2 * 32; Hd.F = s->feat; Hd.FK = (s->feat + 15) / 16 * 16; Hd.n_action = s->n_action; Hd.actions = actions; Hd.q = q; Hd.xout = (bf16x8 *)x;
+    if (x) hipLaunchKernelGGL((k_dqn_head<false, true>), dim3(head_grid), dim3(HEAD_THREADS), HEAD_LDS, st, Hd);
+    else if (stamps_on) {
         Hd.stamps = d_stamps + (size_t)grid * 8;
         hipLaunchKernelGGL(k_dqn_head<true>, dim3(head_grid), dim3(HEAD_THREADS), HEAD_LDS, st, Hd);
         std::vector<long long> h((size_t)(grid + head_grid) * 8);
@@ -660,3 +681,8 @@ int policy_dqn_infer_bf16(const PolicyDqnShape *s, const PolicyDqnWeights *w, co
 }
 
 }  // extern "C"
+
+int magent_amd::bf16::dqn_trunk(const PolicyDqnShape *s, const PolicyDqnWeights *w, const void *view_any, bool cells16, const float *feat, int n,
+                                void *act_workspace, void *x, void *stream) {
+    return x ? dqn_infer(s, w, view_any, cells16, feat, n, act_workspace, nullptr, nullptr, stream, x) : 1;
+}

@@ -40,7 +40,7 @@
 
 namespace {
 
-using namespace magent_amd::f32;      // the vector types, mfma4, and the shared blocks: pingpong, head_gemm512, q_epilogue
+using namespace magent_amd::f32;      // the vector types, mfma4, and the shared blocks: pingpong, head_gemm512, q_epilogue, sigmoid
 
 constexpr int STATE = 512, GRU_TILES = STATE / 32;
 constexpr int GRU_WAVES = 8, GRU_THREADS = 64 * GRU_WAVES, GRU_CHUNK = 4;     // groups of 8 K-values a wave has in flight per buffer
@@ -57,8 +57,6 @@ struct GruArgs {
     const float *bias;        // [4][512] b_ir + b_hr, b_iz + b_hz, b_in, b_hn
     float *out;               // [n][512] h'
 };
-
-__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 
 template <bool HAS_H>
 __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_f32(GruArgs A) {

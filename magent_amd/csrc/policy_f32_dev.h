@@ -9,7 +9,8 @@
 //   hidden_out with the sinks ToX / ToHid            the 128 agents x 256 outputs dense pair (k_dqn_head_f32, k_a2c_trunk_f32)
 //   head_gemm512                                     the one-wave K = 512, 32-output head GEMM (k_drqn_head_f32, k_a2c_head_f32)
 //   q_epilogue                                       the dueling combination, torch.argmax's pick, the stores (k_dqn_head_f32, k_drqn_head_f32)
-//   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32)
+//   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, k_drqn_gru_bf16)
+// policy_drqn_bf16.hip takes out_of, sigmoid, q_epilogue and pingpong from here too (its gates, blend and epilogue are float32).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -34,6 +35,8 @@ __device__ __forceinline__ int out_of(int r, int g) { return (r & 3) + 8 * (r >>
 // relu that keeps a NaN a NaN, as torch.relu does (fmaxf is IEEE maxNum: fmaxf(NaN, 0) = 0, and a poisoned view or a diverged network would
 // then act on finite garbage).  IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950, the cost of the v_max_f32 it replaces; -0 gives +0.
 __device__ __forceinline__ float relu(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
+// the GRU gates' sigmoid (k_drqn_gru_f32, k_drqn_gru_bf16): nothing launders a NaN
+__device__ __forceinline__ float sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
 __device__ __forceinline__ f32x4 relu4(const f32x16 &acc, int q) {
     return f32x4{relu(acc[4 * q]), relu(acc[4 * q + 1]), relu(acc[4 * q + 2]), relu(acc[4 * q + 3])};
 }
