@@ -300,7 +300,7 @@ def synthetic(kind, n, h, w, c, rs, density=0.08):
     feat = (rs.rand(n, 5) * 150).astype(np.float32)          # (the threshold test reads the flattened array)
     v2a = -np.ones((h, w), dtype=np.int32)
     cells = rs.permutation(h * w)[:12]
-    v2a.reshape(-1)[cells] = np.arange(12)
+    v2a.reshape(-1)[cells] = np.arange(len(cells))           # (a view of fewer than 12 cells: all of them)
     return view, feat, {"base": 13, "v2a": v2a, "threshold": 100.0, "move_back": 4, "channel": 3 if kind != "gather" else 0}
 
 
