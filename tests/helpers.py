@@ -4,6 +4,7 @@ One driver, three engines: the product (HIP, magent_amd/lib/libmagent.so), the C
 (oracle/liboracle.so) and -- when present -- the compiled reference (oracle/_ref/libmagent_ref.so).
 All are driven through the same magent_amd.GridWorld wrapper with the same seeds and action streams.
 """
+import ctypes
 import hashlib
 import os
 import subprocess
@@ -1642,6 +1643,438 @@ def scenarios():
                  over={"small": {"damage": 12}}),
     ]
     return {s.name: s for s in S}
+
+
+# ---------------------------------------------------------------------------------------------------- caller-owned output buffers under guard
+# (tests/test_engine_buffers.py, tools/mutation_buffers.py)
+GUARD_BYTES = 64 * 1024            # a workgroup's worth of stray 16-byte stores (256 x 16 B = 4 KiB) lands well inside
+# a word no correct output holds: a NaN with a payload for float32 (the engine's own NaN is 0xFFC00000) -- as an id, a position or a
+# float's bits in int32 it is 2,141,570,017; a bf16 NaN with a payload; a byte that is neither 0 nor 1
+SENTINEL = {4: 0x7FA5C3E1, 2: 0x7FA5, 1: 0xA5}
+_GUARD_TYPES = {"float32": (4, np.float32), "int32": (4, np.int32), "bfloat16": (2, np.uint16), "bool": (1, np.uint8)}
+_WORD_TYPES = {4: np.uint32, 2: np.uint16, 1: np.uint8}
+
+
+class Guarded(object):
+    """one allocation [guard | interior | guard] of sentinel words (guarded): `words` the whole allocation as integer words from a 16-byte
+    boundary on, `front` the interior's first word, `n` rows of `row` words in use of `cap`, `interior` the n rows as a contiguous view, `ptr`
+    its address (valid for zero rows too)"""
+
+
+def guarded(shape, dtype, lib_or_dev, offset_elems=0, capacity_rows=None):
+    """A caller-owned output buffer of `shape` (rows first) between two guards of at least 64 KiB, everything prefilled with the sentinel of the
+    element size (SENTINEL).  dtype: "float32", "int32", "bfloat16" or "bool" (one byte per element).  lib_or_dev: "numpy" (the host ABI), a
+    torch.device, or an engine library's path / None (the device its *_device calls take: helpers.is_emu -> CPU tensors, else cuda:0).  The
+    interior starts `offset_elems` elements behind a 16-byte boundary; capacity_rows >= shape[0] makes it that many rows long, as the
+    wrapper's cached observation buffers are (buf[:n]) -- the rows past shape[0] count as guard.  A zero-row interior is a valid pointer
+    into the allocation."""
+    word, np_type = _GUARD_TYPES[dtype]
+    n, row = int(shape[0]), int(np.prod(shape[1:], dtype=np.int64))
+    cap = n if capacity_rows is None else int(capacity_rows)
+    assert cap >= n and 0 <= offset_elems * word < 4096
+    front = GUARD_BYTES // word + offset_elems
+    total = front + cap * row + GUARD_BYTES // word
+    g = Guarded()
+    g.word, g.sentinel, g.front, g.n, g.row, g.cap, g.dtype, g.offset = word, SENTINEL[word], front, n, row, cap, dtype, offset_elems
+    if isinstance(lib_or_dev, str) and lib_or_dev == "numpy":
+        raw = np.full(total + 16 // word, g.sentinel, dtype=_WORD_TYPES[word])
+        shift = (-raw.ctypes.data % 16) // word
+        g.words = raw[shift:shift + total]
+        assert g.words.ctypes.data % 16 == 0
+        g.interior = g.words[front:front + n * row].view(np_type).reshape(tuple(shape))
+        g.ptr = g.words.ctypes.data + front * word
+        assert n * row == 0 or g.interior.ctypes.data == g.ptr
+    else:
+        import torch
+        dev = lib_or_dev if isinstance(lib_or_dev, torch.device) else torch.device("cpu") if is_emu(lib_or_dev) else torch.device("cuda", 0)
+        wt = {4: torch.int32, 2: torch.int16, 1: torch.uint8}[word]
+        raw = torch.full((total + 16 // word,), g.sentinel, dtype=wt, device=dev)
+        shift = (-raw.data_ptr() % 16) // word
+        g.words = raw[shift:shift + total]
+        assert g.words.data_ptr() % 16 == 0
+        tt = {"float32": torch.float32, "int32": torch.int32, "bfloat16": torch.bfloat16, "bool": torch.uint8}[dtype]
+        g.interior = g.words[front:front + n * row].view(tt).view(tuple(shape))
+        g.ptr = g.words.data_ptr() + front * word      # (a zero-row view of torch's or NumPy's does not keep its address: the calls take this)
+        assert g.interior.is_contiguous() and (n * row == 0 or g.interior.data_ptr() == g.ptr)
+    return g
+
+
+def _guard_words(g):
+    """the whole allocation on the host, as unsigned integer words"""
+    w = g.words if isinstance(g.words, np.ndarray) else g.words.cpu().numpy()
+    return w.view(_WORD_TYPES[g.word])
+
+
+def assert_guards_intact(g, tag):
+    """both guards and the rows past n still hold the sentinel -- compared as integer words"""
+    w = _guard_words(g)
+    end = g.front + g.n * g.row
+    bad = np.flatnonzero(w != g.sentinel)
+    bad = bad[(bad < g.front) | (bad >= end)]
+    assert bad.size == 0, ("%s: %d words outside the %d x %d-word interior (offset %d elements, %d rows of capacity) were written: first %+d, last %+d "
+                           "words from the interior's end (0 is the first word behind it; below %d: in front of the buffer), first value 0x%X"
+                           % (tag, bad.size, g.n, g.row, g.offset, g.cap, bad[0] - end, bad[-1] - end, -g.n * g.row, int(w[bad[0]])))
+
+
+def assert_interior(g, want, tag):
+    """the interior, bit for bit `want` (an array of the oracle's: it must not hold the sentinel itself, so that a word still holding it was
+    never written) -- compared as integer words"""
+    got = _guard_words(g)[g.front:g.front + g.n * g.row]
+    ww = np.ascontiguousarray(want).reshape(-1).view(_WORD_TYPES[g.word])
+    assert ww.size == got.size, "%s: the oracle has %d words, the buffer %d" % (tag, ww.size, got.size)
+    assert not bool((ww == g.sentinel).any()), "%s: the oracle's output holds the sentinel word" % tag
+    bad = np.flatnonzero(got != ww)
+    assert bad.size == 0, ("%s: %d of %d interior words differ from the oracle's, %d of them were never written (sentinel); first at word %d (row %d): "
+                           "0x%X, oracle 0x%X; last at word %d" % (tag, bad.size, got.size, int((got[bad] == g.sentinel).sum()), bad[0], bad[0] // max(g.row, 1),
+                                                                   int(got[bad[0]]), int(ww[bad[0]]), bad[-1]))
+
+
+def assert_all_written(g, tag):
+    """no word of the interior still holds the sentinel (outputs without a host getter of the oracle's to compare with)"""
+    got = _guard_words(g)[g.front:g.front + g.n * g.row]
+    left = np.flatnonzero(got == g.sentinel)
+    assert left.size == 0, "%s: %d of %d interior words were never written, first at word %d" % (tag, left.size, got.size, left[0])
+
+
+BUFFER_BATTLE_PAIRS = [(1, 2), (63, 65), (64, 257), (255, 256), (509, 3)]
+BUFFER_BATTLES = ["battle_%d_%d" % p for p in BUFFER_BATTLE_PAIRS]
+BUFFER_SHAPES = ["gather", "pursuit_dense", "quad", "battle_turn", "bodies", "arrange", "arrange_turn", "arrange_two_turn", "battle_empty_side"]
+# (view offset, feature offset) in floats: both 16-byte aligned (the vector path and its tail), both not (the scalar path), one of each (the
+# stand-alone k_features launch)
+BUFFER_OFFSETS = [(0, 0), (4, 4), (1, 1), (2, 2), (3, 3), (0, 1), (1, 0)]
+# bf16 cells: the view 16-byte aligned always (the engine refuses another with fatal()); the feature pointer is free -- Env::prepare_render
+# compares the two alignments and Env::observe_device sends a feature pointer of another alignment to the stand-alone launch
+BUFFER_OFFSETS_BF16 = [(0, 0), (8, 4), (0, 1), (8, 3)]
+
+
+def buffer_worlds():
+    """the worlds of tests/test_engine_buffers.py, three steps each: battle 45 x 45 at group sizes around the render kernels' edges (a wave's 64
+    cells, a workgroup's 256 threads, odd n -- n x 1183 floats is then no multiple of 4 --, the smallest world; hp 4 / damage 3 so that
+    clear_dead shrinks the dense ones), one world per shape launch_render tells apart (scenarios(): gather -- two windows, 7 channels;
+    pursuit_dense -- 5 channels, no minimap; quad -- unpacked view cells, 13 channels; battle_turn -- the packed TURN forms; bodies -- three
+    groups of multi-cell bodies; arrange -- two groups with a can_absorb type: unpacked cells AND 7 channels, the only way to
+    k_render_cells16<PACKED = false>; arrange_turn -- three such groups under turn_mode: k_render<PACKED = false, TURN = true>;
+    arrange_two_turn -- arrange's two groups under turn_mode: k_render_cells16<false, true>), a world whose second group is empty, and battle60
+    (2400 agents: beyond the two-launch cycle)"""
+    import copy
+    rnd = lambda g, n: (g, "random", {"n": n})
+    W = {}
+    for a, b in BUFFER_BATTLE_PAIRS:
+        W["battle_%d_%d" % (a, b)] = Scenario("battle_%d_%d" % (a, b), "battle", 45, seed=700 + a, place=[rnd(0, a), rnd(1, b)], steps=3,
+                                              action_seed=7 * a + b, over={"small": {"hp": 4, "damage": 3}})
+    for name in ("gather", "pursuit_dense", "quad", "battle_turn", "bodies", "arrange", "arrange_turn", "battle60"):
+        W[name] = copy.copy(scenarios()[name])
+        W[name].steps, W[name].events = 3, {}
+    W["arrange_two_turn"] = Scenario("arrange_two_turn", ("arrange", 40, False), 0, place=[rnd(0, 180), rnd(1, 300)], walls=60, acting=[1], steps=3,
+                                     action_seed=79, settings={"turn_mode": True})
+    W["battle_empty_side"] = Scenario("battle_empty_side", "battle", 12, seed=77, place=[rnd(0, 40)], steps=3, action_seed=78)
+    return W
+
+
+def tune_settings():
+    """this process's MAGENT_TUNE as a dict of ints"""
+    return {k: int(v) for k, v in (e.split("=") for e in os.environ.get("MAGENT_TUNE", "").split(",") if e)}
+
+
+def play_buffer_world(sc, lib, clear_last=True):
+    """`sc` on library `lib`, played for its steps with the scenario's random actions through the host calls, clear_dead behind every step (behind
+    the last one only with clear_last).  Returns the environment, its handles, the group sizes at the start and the action generator."""
+    env, handles = sc.build(lib)
+    n0 = [env.get_num(h) for h in handles]
+    rs = np.random.RandomState(sc.action_seed)
+    acting = sc.acting if sc.acting is not None else list(range(len(handles)))
+    for step in range(sc.steps):
+        for g, h in enumerate(handles):
+            if g in acting:
+                env.set_action(h, sc.draw(rs, env, g, h, env.get_num(h)))
+        env.step()
+        if clear_last or step + 1 < sc.steps:
+            env.clear_dead()
+    return env, handles, n0, rs
+
+
+_BUFFER_WANT = {}
+
+
+def buffer_expectations(name):
+    """what the oracle returns for buffer world `name` through the plain host calls (computed once per process, never changed):
+    "n0" the sizes at the start (capacity of the guarded buffers: n0 + 1 rows); "pre": behind the third step, the dead still there -- reward, id,
+    alive, pos per group; "post": behind its clear_dead -- view, feat, reward, id, alive, pos, view2attack per group, mean_info of the acting
+    non-empty ones, the 5 x 6 global minimap; "acts" / "cycle_reward": the fourth step's actions and the rewards behind it (what
+    env_cycle_many hands out for the observations of "post")"""
+    if name in _BUFFER_WANT:
+        return _BUFFER_WANT[name]
+    sc = buffer_worlds()[name]
+    env, hs, n0, rs = play_buffer_world(sc, ensure_oracle(), clear_last=False)
+    acting = sc.acting if sc.acting is not None else list(range(len(hs)))
+    state = lambda h: {"reward": np.array(env.get_reward(h), dtype=np.float32), "id": env.get_agent_id(h).copy(), "alive": env.get_alive(h).astype(np.uint8),
+                       "pos": env.get_pos(h).copy(), "n": env.get_num(h)}
+    want = {"n0": n0, "pre": [state(h) for h in hs], "acting": acting}
+    for g, h in enumerate(hs):         # (the dead still in the arrays: what the hp getter's rows of the living are compared with)
+        if want["pre"][g]["n"] > 0:
+            want["pre"][g]["view"] = env.get_observation(h)[0].copy()
+    env.clear_dead()
+    want["post"] = [state(h) for h in hs]
+    for g, h in enumerate(hs):
+        p = want["post"][g]
+        if p["n"] > 0:
+            v, f = env.get_observation(h)
+            p["view"], p["feat"] = v.copy(), f.copy()
+            if g in acting:
+                p["mean_info"] = env.get_mean_info(h).copy()
+        else:
+            p["view"] = np.zeros((0,) + env.get_view_space(h), dtype=np.float32)
+            p["feat"] = np.zeros((0,) + env.get_feature_space(h), dtype=np.float32)
+        p["view2attack"] = env.get_view2attack(h)[1].copy()
+    want["global_minimap"] = env.get_global_minimap(5, 6).copy()
+    want["acts"] = [sc.draw(rs, env, g, h, env.get_num(h)) if g in acting else None for g, h in enumerate(hs)]
+    for g, h in enumerate(hs):
+        if want["acts"][g] is not None:
+            env.set_action(h, want["acts"][g])
+    want["cycle_done"] = env.step()
+    want["cycle_reward"] = [np.array(env.get_reward(h), dtype=np.float32) for h in hs]
+    env.clear_dead()
+    want["cycle_n"] = [env.get_num(h) for h in hs]
+    _BUFFER_WANT[name] = want
+    return want
+
+
+def bf16_cells(view):
+    """the bf16-cell form of a float32 view [n, H, W, C <= 7] as uint16 [n, H, W, 8]: the channels rounded to nearest even on the bits (a NaN
+    keeps its sign and the upper half of its payload, quiet: the IEEE conversion -- the engine's 0xFFC00000 of an empty group's minimap becomes
+    0xFFC0; torch's own conversions disagree with each other on NaNs), zeros up to channel 6, 1.0 in channel 7 (include/magent_policy.h)"""
+    C = view.shape[-1]
+    out = np.zeros(view.shape[:-1] + (8,), dtype=np.uint16)
+    if view.size:
+        u = np.ascontiguousarray(view).view(np.uint32).astype(np.uint64)
+        rne = (u + 0x7FFF + ((u >> 16) & 1)) >> 16
+        out[..., :C] = np.where((u & 0x7FFFFFFF) > 0x7F800000, (u >> 16) | 0x40, rne).astype(np.uint16)
+    out[..., 7] = 0x3F80
+    return out
+
+
+def expected_render_kernel(sc, env, handles, g, n, aligned, cells16):
+    """launch_render (render.hip) restated: the kernel engine_stats()[6] must name for a render of group g -- 0 k_render / k_render_cells16,
+    1 k_render_fast, 4 k_render_sweep2 -- under this process's MAGENT_TUNE.  A second copy of the dispatch, to be kept in step with
+    render.hip: render_fast_ok (its render_fast_lds(VHW) <= 48 KiB term holds for every window of these worlds and is left out), sweep5_ok
+    and the `mode` selection in launch_render"""
+    cfg = sc.config()
+    turn, food, minimap = (bool(cfg.config_dict.get(k)) for k in ("turn_mode", "food_mode", "minimap_mode"))
+    H, W, C = env.get_view_space(handles[g])
+    packed = len(handles) <= 3 and not any(t.get("can_absorb") for t in cfg.agent_type_dict.values())
+    shape = aligned and len(handles) == 2 and not food and not turn and packed and 16 <= H * W <= 1024
+    fast_ok = shape and minimap and C == 7
+    sweep5_ok = shape and not minimap and C == 5 and not cells16
+    if not (fast_ok or sweep5_ok):
+        return 0
+    mode = tune_settings().get("render", -1)
+    if mode < 0:
+        mode = 1 if cells16 else 4 if (n * H * W + 63) // 64 >= 256 * 4 * 2 * 8 else 0
+    return 4 if mode == 4 else 1 if mode == 1 and fast_ok else 0
+
+
+def check_observation_buffers(lib, name, offsets=None, offsets_bf16=None):
+    """env_get_observation_device and ..._bf16 of buffer world `name` on library `lib` into guarded views and feature rows at every offset
+    pair: interior == the oracle's bits, guards and the rows past n untouched; which render kernel ran and whether the feature rows took a
+    launch of their own is asserted from the engine's own counters.  Returns the set of (kernel, cells16) pairs seen."""
+    sc, want = buffer_worlds()[name], buffer_expectations(name)
+    env, hs, n0, _ = play_buffer_world(sc, lib)
+    dev = torch_device(env, lib)
+    env.profile_enable(1)
+    seen = set()
+    for g, h in enumerate(hs):
+        n, p = env.get_num(h), want["post"][g]
+        assert n == p["n"], (name, g, n, p["n"])
+        vs, fs, cap = env.get_view_space(h), env.get_feature_space(h), n0[g] + 1
+        forms = [(False, vo, fo) for vo, fo in (BUFFER_OFFSETS if offsets is None else offsets)]
+        if vs[2] <= 7:        # (the wrapper refuses bf16 cells for more channels; the engine would abort)
+            forms += [(True, vo, fo) for vo, fo in (BUFFER_OFFSETS_BF16 if offsets_bf16 is None else offsets_bf16)]
+        for cells16, vo, fo in forms:
+            tag = "%s group %d (n %d) %s view+%d feat+%d" % (name, g, n, "bf16 cells" if cells16 else "float32", vo, fo)
+            gv = guarded((n,) + vs[:2] + (8,), "bfloat16", dev, vo, cap) if cells16 else guarded((n,) + vs, "float32", dev, vo, cap)
+            gf = guarded((n,) + fs, "float32", dev, fo, cap)
+            v_aligned, f_aligned = gv.ptr % 16 == 0, gf.ptr % 16 == 0
+            assert v_aligned == (vo * gv.word % 16 == 0) and f_aligned == (fo % 4 == 0) and (v_aligned or not cells16), tag
+            device_sync(lib)
+            env.profile_read("render"), env.profile_read("features")
+            (env._lib.env_get_observation_device_bf16 if cells16 else env._lib.env_get_observation_device)(env.game, g, (ctypes.c_void_p * 2)(gv.ptr, gf.ptr))
+            env.sync()
+            assert_interior(gv, bf16_cells(p["view"]) if cells16 else p["view"], tag + " view")
+            assert_guards_intact(gv, tag + " view")
+            assert_interior(gf, p["feat"], tag + " feat")
+            assert_guards_intact(gf, tag + " feat")
+            renders, own_features = env.profile_read("render")[0], env.profile_read("features")[0]
+            if n == 0:
+                assert renders == 0 and own_features == 0, tag
+                continue
+            kernel = env.engine_stats()[6]
+            assert kernel == expected_render_kernel(sc, env, hs, g, n, v_aligned, cells16), (tag, "render kernel", kernel)
+            assert renders == 1 and own_features == (1 if v_aligned != f_aligned else 0), (tag, renders, own_features)
+            seen.add((kernel, cells16))
+    return seen
+
+
+def check_getter_buffers(lib, name):
+    """env_get_reward_device and env_get_info_device (every name Env::info_device takes: id, hp, pos, alive) of buffer world `name` into
+    guarded buffers, behind the third step with the dead still in the arrays and again behind clear_dead, against the oracle's host getters.
+    The oracle has no getter for hp: every byte must have been written, and where every agent is one cell and nobody turns the window's
+    centre cell of the oracle's observation, hp / type hp, must be the float32 quotient of what was written -- in both phases, for every agent
+    that is alive."""
+    sc, want = buffer_worlds()[name], buffer_expectations(name)
+    env, hs, n0, _ = play_buffer_world(sc, lib, clear_last=False)
+    dev = torch_device(env, lib)
+    cfg = sc.config()
+    for phase in ("pre", "post"):
+        if phase == "post":
+            env.clear_dead()
+        for g, h in enumerate(hs):
+            n, p, cap = env.get_num(h), want[phase][g], n0[g] + 1
+            assert n == p["n"], (name, phase, g, n, p["n"])
+            tag = "%s %s group %d (n %d)" % (name, phase, g, n)
+            for off in (0, 1):
+                bufs = {"reward": guarded((n,), "float32", dev, off, cap), "id": guarded((n,), "int32", dev, off, cap),
+                        "hp": guarded((n,), "float32", dev, off, cap), "pos": guarded((n, 2), "int32", dev, 2 * off, cap),
+                        "alive": guarded((n,), "bool", dev, off, cap)}
+                device_sync(lib)
+                env._lib.env_get_reward_device(env.game, g, ctypes.c_void_p(bufs["reward"].ptr))
+                for key in ("id", "hp", "pos", "alive"):
+                    env._lib.env_get_info_device(env.game, g, key.encode(), ctypes.c_void_p(bufs[key].ptr))
+                env.sync()
+                for key, b in bufs.items():
+                    if key == "hp":
+                        assert_all_written(b, "%s hp+%d" % (tag, off))
+                    else:
+                        assert_interior(b, p[key], "%s %s+%d" % (tag, key, off))
+                    assert_guards_intact(b, "%s %s+%d" % (tag, key, off))
+                t = cfg.agent_type_dict[cfg.groups[g]]
+                if n > 0 and t.get("width") == t.get("length") == 1 and "hp" in t and not cfg.config_dict.get("turn_mode") and isinstance(t.get("view_range"), gw.CircleRange):
+                    hp = _guard_words(bufs["hp"])[bufs["hp"].front:bufs["hp"].front + n].view(np.float32)
+                    vh, vw = p["view"].shape[1:3]
+                    own = 1 + (1 if cfg.config_dict.get("food_mode") else 0) + 1      # [wall | (food) | own has, own hp ...]
+                    ratio = (hp / np.float32(t["hp"])).astype(np.float32)
+                    live = p["alive"].astype(bool)                                    # (a dead agent has left its cell)
+                    assert ratio[live].view(np.uint32).tobytes() == np.ascontiguousarray(p["view"][live, vh // 2, vw // 2, own]).view(np.uint32).tobytes(), tag + " hp"
+
+
+def check_cycle_buffers(lib, names, leave_out=None):
+    """one env_cycle_many call (EnvBatch.cycle) over buffer worlds `names` behind their three steps, with caller-owned views, feature rows and
+    rewards under guard (float offset 0: the batched forms take 16-byte aligned buffers only): the observations of "post" and the rewards behind
+    the fourth step, bit for bit the oracle's; guards and rows past n untouched.  leave_out: a group whose view / feat / reward entries are
+    NULL (it still acts).  Which form the call took -- the two-launch cycle, the call sequence, the batched pipeline, its sweeping render, a
+    world's own render launches -- is asserted from the engine's counters under this process's MAGENT_TUNE."""
+    import torch
+    tune = tune_settings()
+    worlds = [(buffer_worlds()[nm], buffer_expectations(nm)) + play_buffer_world(buffer_worlds()[nm], lib) for nm in names]
+    envs = [w[2] for w in worlds]
+    dev = torch_device(envs[0], lib)
+    batch = magent_amd.EnvBatch(envs, n_threads=1)
+    batch.order_streams = not is_emu(lib)
+    views, feats, acts, rews, keep = [], [], [], [], []
+    for sc, want, env, hs, n0, _ in worlds:
+        nums = [env.get_num(h) for h in hs]
+        assert nums == [p["n"] for p in want["post"]], (sc.name, nums)
+        seen = [g != leave_out for g in range(len(hs))]
+        views.append([guarded((nums[g],) + env.get_view_space(h), "float32", dev, 0, n0[g] + 1) if seen[g] else None for g, h in enumerate(hs)])
+        feats.append([guarded((nums[g],) + env.get_feature_space(h), "float32", dev, 0, n0[g] + 1) if seen[g] else None for g, h in enumerate(hs)])
+        rews.append([guarded((nums[g],), "float32", dev, 0, n0[g] + 1) if seen[g] else None for g in range(len(hs))])
+        acts.append([None if a is None else torch.from_numpy(a).to(dev) for a in want["acts"]])
+        env.profile_enable(1)
+        env.profile_read("render")
+        keep.append(nums)
+    device_sync(lib)
+    def inner(rows):      # (EnvBatch.pointers, from the guarded buffers' own addresses)
+        arr = (ctypes.c_void_p * (len(envs) * batch.n_group))()
+        for e, row in enumerate(rows):
+            for g, b in enumerate(row):
+                arr[e * batch.n_group + g] = None if b is None else b.ptr
+        return arr
+    dones = batch.cycle(inner(views), inner(feats), acts, inner(rews))
+    out = []
+    for k, (sc, want, env, hs, n0, _) in enumerate(worlds):
+        env.sync()
+        assert bool(dones[k]) == bool(want["cycle_done"]) and [env.get_num(h) for h in hs] == want["cycle_n"], sc.name
+        for g in range(len(hs)):
+            if views[k][g] is None:
+                continue
+            tag = "%s group %d (n %d) env_cycle_many of %d%s" % (sc.name, g, keep[k][g], len(names), "" if leave_out is None else ", group %d left out" % leave_out)
+            for b, w, what in ((views[k][g], want["post"][g]["view"], "view"), (feats[k][g], want["post"][g]["feat"], "feat"), (rews[k][g], want["cycle_reward"][g], "reward")):
+                assert_interior(b, w, tag + " " + what)
+                assert_guards_intact(b, tag + " " + what)
+        renders, piped, swept = env.profile_read("render")[0], env.pipeline_stats()[6], env.pipeline_stats()[7]
+        observed = sum(1 for g in range(len(hs)) if views[k][g] is not None and keep[k][g] > 0)
+        cells = max([keep[k][g] * int(np.prod(env.get_view_space(h)[:2])) for g, h in enumerate(hs) if views[k][g] is not None] + [0])
+        out.append((sc.name, renders, piped, swept))
+        if sc.name not in BUFFER_BATTLES + ["battle60"]:      # (the plain two-group worlds: their forms are restated here)
+            continue
+        # (Env::cycle_many: the pipeline takes a plain world that cannot step in one launch, or one of batch_pipe_min agents or more)
+        in_pipe = len(names) >= 2 and (tune.get("batch_pipe_min", 1537) <= sum(keep[k]) or tune.get("solo_step", 1) == 0)
+        assert piped == (1 if in_pipe else 0), (sc.name, "batched pipeline", out)
+        if in_pipe:         # a world of a group of pipe_own x 65536 window cells renders by launches of its own, the others in the batch's launch
+            own = cells >= 65536 * tune.get("pipe_own", 48)
+            assert renders == (observed if own else 0) and swept == (1 if tune.get("pipe_sweep", -1) != 0 and not own else 0), (sc.name, "pipeline render", out)
+        elif len(names) == 1:
+            two_launch = tune.get("solo_step", 1) != 0 and sum(keep[k]) <= 1536
+            assert renders == (1 if two_launch else observed), (sc.name, "two-launch cycle" if two_launch else "call sequence", out)
+            if not two_launch and sum(keep[k]) > 0:
+                assert (env.engine_stats()[7] > 0) == (sum(keep[k]) > 1536 or tune.get("solo_step", 1) == 0), (sc.name, "plain pipeline", env.engine_stats())
+    return out
+
+
+def check_host_abi_buffers(lib, name):
+    """the host ABI of library `lib` (reached through the wrapper's own handle) with NumPy interiors carved from guarded arrays: env_get_observation,
+    env_get_reward, env_get_info for id, alive, pos, mean_info, view2attack and a 5 x 6 global_minimap -- the device-to-host copies have sizes of
+    their own"""
+    sc, want = buffer_worlds()[name], buffer_expectations(name)
+    env, hs, n0, _ = play_buffer_world(sc, lib)
+    L = env._lib
+    ptr = lambda b: ctypes.c_void_p(b.ptr)
+    for g, h in enumerate(hs):
+        n, p, cap = env.get_num(h), want["post"][g], n0[g] + 1
+        assert n == p["n"], (name, g, n, p["n"])
+        for off in (0, 1):
+            tag = "%s group %d (n %d) host ABI +%d" % (name, g, n, off)
+            gv = guarded((n,) + env.get_view_space(h), "float32", "numpy", off, cap)
+            gf = guarded((n,) + env.get_feature_space(h), "float32", "numpy", off, cap)
+            L.env_get_observation(env.game, g, (ctypes.c_void_p * 2)(ptr(gv), ptr(gf)))
+            gr = guarded((n,), "float32", "numpy", off, cap)
+            L.env_get_reward(env.game, g, ptr(gr))
+            checks = [(gv, p["view"], "view"), (gf, p["feat"], "feat"), (gr, p["reward"], "reward")]
+            for key, shape, dtype in (("id", (n,), "int32"), ("alive", (n,), "bool"), ("pos", (n, 2), "int32")):
+                b = guarded(shape, dtype, "numpy", off * (2 if key == "pos" else 1), cap)
+                L.env_get_info(env.game, g, key.encode(), ptr(b))
+                checks.append((b, p[key], key))
+            b = guarded(p["view2attack"].shape, "int32", "numpy", off)
+            L.env_get_info(env.game, g, b"view2attack", ptr(b))
+            checks.append((b, p["view2attack"], "view2attack"))
+            if "mean_info" in p:
+                b = guarded(p["mean_info"].shape, "float32", "numpy", off)
+                L.env_get_info(env.game, g, b"mean_info", ptr(b))
+                checks.append((b, p["mean_info"], "mean_info"))
+            for b, w, what in checks:
+                assert_interior(b, w, tag + " " + what)
+                assert_guards_intact(b, tag + " " + what)
+    for off in (0, 3):
+        b = guarded((5, 6, len(hs)), "float32", "numpy", off)
+        b.interior.reshape(-1)[:2] = 5, 6          # (the in-params travel in the out-buffer's first two floats, GridWorld.cc:741-742)
+        L.env_get_info(env.game, -1, b"global_minimap", ptr(b))
+        assert_interior(b, want["global_minimap"], "%s host ABI global_minimap 5 x 6 +%d" % (name, off))
+        assert_guards_intact(b, "%s host ABI global_minimap 5 x 6 +%d" % (name, off))
+
+
+def check_engine_buffer_forms(lib):
+    """what a child process of tests/test_engine_buffers.py runs under its MAGENT_TUNE (read once per process): the battle pairs, gather and
+    pursuit_dense through the observation check (aligned at two offsets, one unaligned pair, the stand-alone feature launch; bf16 cells) and the
+    cycle check alone, then three battle worlds in one EnvBatch -- the checks assert which kernel and which form ran.  Returns what ran."""
+    ran = {"renders": set(), "cycles": []}
+    for name in BUFFER_BATTLES + ["gather", "pursuit_dense"]:
+        ran["renders"] |= check_observation_buffers(lib, name, offsets=[(0, 0), (4, 4), (3, 3), (0, 1)], offsets_bf16=[(0, 0), (8, 1)])
+        ran["cycles"] += check_cycle_buffers(lib, [name])
+    ran["cycles"] += check_cycle_buffers(lib, ["battle_63_65", "battle_509_3", "battle_255_256"])
+    tune = tune_settings()
+    if "render" in tune:
+        assert (tune["render"] if tune["render"] in (1, 4) else 0, False) in ran["renders"], ran
+    ran["renders"] = sorted(ran["renders"])
+    return ran
 
 
 # ---------------------------------------------------------------------------------------------------- the DQN in float64
