@@ -7,7 +7,8 @@
  * C entry point here (its model is a TensorFlow graph); the Python binding is magent_amd/builtin/torch_model/hip_policy.py.
  *
  * Further down: the same network in float32, the deep recurrent Q network's acting step in float32 and with bf16 operands
- * (policy_drqn_infer_f32, policy_drqn_infer), and the actor-critic's.
+ * (policy_drqn_infer_f32, policy_drqn_infer), and the actor-critic's in float32 and with bf16 operands (policy_a2c_infer_f32,
+ * policy_a2c_infer).
  *
  * All pointers are DEVICE pointers; the call enqueues two kernels on `stream` and returns.  Inputs are the engine's own
  * observation tensors (env_get_observation_device): view float[n][view_h][view_w][view_c], feature float[n][feat].
@@ -197,6 +198,52 @@ int policy_a2c_f32_workspace_bytes(const PolicyDqnShape *shape, int n, int use_c
  * not supported / a pointer is missing / the workspace is misaligned / a launch failed. */
 int policy_a2c_infer_f32(const PolicyDqnShape *shape, const PolicyA2cWeightsF32 *weights, const float *view, const float *feature, int n,
                          const float *u, void *workspace, int *actions, float *policy, float *value, void *stream);
+
+/* ---- the same actor-critic step with bf16 matrix operands (v_mfma_f32_32x32x16_bf16) -- magent_amd/csrc/policy_a2c_bf16.hip: an opt-in, as
+ * policy_drqn_infer is beside policy_drqn_infer_f32.
+ * Rounded to bf16 (nearest even): the views (the cells entry takes the engine's cells as they are), the features, every weight matrix, and
+ * every inter-layer activation ONCE, when it is stored: x = [relu(dense_view) | relu(dense_emb)], h0 = relu(dense), each CommNet step's
+ * output -- rows bf16[n][512] in natural unit order (no slot permutation anywhere).  The stored row is what everything downstream reads:
+ * the next layer's operand, the CommNet `skip` term and the column sums.  others_i = (sum - h_i) / (n - 1) is formed in float32 from the
+ * float32 column sum and the stored row, then rounded as the operand (zeros for n == 1).  Everything else is float32: accumulation, all
+ * biases (added behind the MFMA), relu and tanh, the column sums (over blocks of 256 agents in agent order, then over the blocks in order:
+ * no atomics), the logits, the softmax, the clamp, the value and the draw (policy_a2c_infer_f32's, the same code).
+ * Weights in (bf16) fragment order (PolicyDqnWeights: k-step s, tile T, lane l holds W[32 T + (l & 31)][16 s + 8 (l >> 5) + 0..7]),
+ * outputs and biases in natural order:
+ *   dense_view       : K = view_h * view_w * view_c in the float32 view's order, padded to a multiple of 16 with zero weights   [KP/16][8][64][8]
+ *   dense_view_cells : the same matrix for the engine's cells [view_h][view_w][8]: K' = 8 view_h view_w, k = 8 cell + channel, padded to a
+ *                      multiple of 16 (one cell); zero weights for channels >= view_c, so the cells' constant 1.0 in channel 7 meets
+ *                      a zero.  NULL where the shape has no cells (view_c > 7 or K' > 4096)                             [K'P/16][8][64][8]
+ *   dense_emb        : feature index, padded to a multiple of 16                                                         [FK/16][8][64][8]
+ *   dense            : K = dense_view's 256 units, then dense_emb's 256                                                  [32][16][64][8]
+ *   comm[s]          : CommNet step s = 0, 1 (use_comm): C_s and H_s side by side, K = the 512 means of the OTHER agents' units, then the
+ *                      agent's own 512; NULL without use_comm                                                            [64][16][64][8]
+ *   head             : K = the 512 hidden units; outputs 0..n_action-1 = policy logits, output n_action = value, the rest zero  [32][1][64][8]
+ * dense_view_bias, dense_emb_bias float[256]; dense_bias float[512]; head_bias float[32]: as for PolicyA2cWeightsF32. */
+typedef struct {
+    const void *dense_view, *dense_view_cells, *dense_emb, *dense;
+    const void *comm[2];
+    const void *head;
+    const float *dense_view_bias, *dense_emb_bias, *dense_bias, *head_bias;
+    int use_comm;
+} PolicyA2cWeights;
+
+/* 0 if the bf16 A2C kernels do not take this shape; otherwise bit 0 is set: policy_a2c_infer (float32 views) takes it --
+ * policy_a2c_f32_supported's region, view_h * view_w * view_c <= 4096, 1 <= feat <= 64, 1 <= n_action <= 31 -- and bit 1 says whether
+ * policy_a2c_infer_bf16 (cells) takes it too: additionally view_c <= 7 and 8 * view_h * view_w <= 4096.  So 0, 1 or 3. */
+int policy_a2c_supported(const PolicyDqnShape *shape);
+/* size of the workspace of one call with n agents: two (use_comm: three) bf16[n][512] layers, and with use_comm the column sums' partial
+ * blocks (float32) */
+int policy_a2c_workspace_bytes(const PolicyDqnShape *shape, int n, int use_comm, size_t *bytes);
+/* One step of n agents: the arguments, the draw, the span of the CommNet means (ALL n agents of the call), the alignment rule (workspace:
+ * 16 bytes) and the return codes of policy_a2c_infer_f32.  Enqueues its kernels (3, with use_comm 9) on `stream`; a refused call has
+ * written nothing. */
+int policy_a2c_infer(const PolicyDqnShape *shape, const PolicyA2cWeights *weights, const float *view, const float *feature, int n,
+                     const float *u, void *workspace, int *actions, float *policy, float *value, void *stream);
+/* the same with the views as the engine's bf16 cells ([n][view_h][view_w][8], channel 7 = 1.0; 16-byte aligned: a cell is one load and one
+ * half of a k-step, nothing is converted); needs weights->dense_view_cells */
+int policy_a2c_infer_bf16(const PolicyDqnShape *shape, const PolicyA2cWeights *weights, const void *view_cells, const float *feature, int n,
+                          const float *u, void *workspace, int *actions, float *policy, float *value, void *stream);
 
 #ifdef __cplusplus
 }

@@ -52,7 +52,7 @@ class _ActorCritic(nn.Module):
 class AdvantageActorCritic(BaseModel):
     def __init__(self, env, handle, name, learning_rate=1e-3, batch_size=64, reward_decay=0.99, eval_obs=None,
                  train_freq=1, value_coef=0.1, ent_coef=0.08, use_comm=False, custom_view_space=None,
-                 custom_feature_space=None, device=None):
+                 custom_feature_space=None, device=None, infer_dtype=None):
         BaseModel.__init__(self, env, handle)
         self.env, self.handle, self.name, self.subclass_name = env, handle, name, "torcha2c"
         self.view_space = tuple(custom_view_space or env.get_view_space(handle))
@@ -68,20 +68,37 @@ class AdvantageActorCritic(BaseModel):
         # Acting on device-resident float32 observations goes through hand-written kernels (magent_amd/csrc/policy_a2c_f32.hip: the network,
         # CommNet included, the softmax and an inverse-CDF draw from torch.rand); MAGENT_POLICY_F32=torch keeps the PyTorch forward pass and
         # torch.multinomial below, as for the DQN.  Numpy inputs, CPU devices and shapes the kernels do not take use that path too.
-        self._hip = None
-        if self.device.type == "cuda" and os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
-            try:
-                from .hip_policy import HipA2cPolicyF32
-                self._hip = HipA2cPolicyF32(self.net, self.view_space, self.feature_space, self.num_actions, self.device)
-            except (ValueError, OSError, AttributeError):
-                self._hip = None
+        # infer_dtype "bf16" (the argument, or MAGENT_POLICY_DTYPE=bf16 for scripts run unmodified) is the DQN's and the DRQN's opt-in: acting
+        # then goes through the bf16 MFMA kernels (magent_amd/csrc/policy_a2c_bf16.hip: bf16 matrix operands and inter-layer rows, float32
+        # accumulation, biases, column sums, softmax and draw) where the shape is theirs, and through what "f32" would use where it is not.
+        # `bf16_kernels` says which.  Training is untouched by it.
+        self.infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
+        if self.infer_dtype not in ("f32", "bf16"):
+            raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (self.infer_dtype,))
+        self._hip, self.bf16_kernels = None, False
+        if self.device.type == "cuda":
+            from . import hip_policy
+            kinds = [hip_policy.HipA2cPolicy] if self.infer_dtype == "bf16" else []
+            if os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
+                kinds.append(hip_policy.HipA2cPolicyF32)
+            for kind in kinds:
+                try:
+                    self._hip = kind(self.net, self.view_space, self.feature_space, self.num_actions, self.device)
+                    self.bf16_kernels = kind is hip_policy.HipA2cPolicy
+                    break
+                except (ValueError, OSError, AttributeError):
+                    self._hip = None
 
     def _on_kernels(self, view, feature):
         n = len(view)
-        return (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
+        if not (self._hip is not None and isinstance(view, torch.Tensor) and isinstance(feature, torch.Tensor) and view.is_cuda
                 and self.device.index in (None, view.device.index)
-                and feature.device == view.device and view.dtype == torch.float32 and feature.dtype == torch.float32 and view.is_contiguous()
-                and feature.is_contiguous() and tuple(view.shape) == (n,) + self.view_space and tuple(feature.shape) == (n,) + self.feature_space)
+                and feature.device == view.device and feature.dtype == torch.float32 and view.is_contiguous()
+                and feature.is_contiguous() and tuple(feature.shape) == (n,) + self.feature_space):
+            return False
+        if view.dtype == torch.bfloat16:     # the engine's bf16 cells [n, H, W, 8]: the bf16 kernels' operands as they are
+            return self.bf16_kernels and self._hip.cells and tuple(view.shape) == (n,) + self.view_space[:2] + (8,)
+        return view.dtype == torch.float32 and tuple(view.shape) == (n,) + self.view_space
 
     def _tensor(self, x, dtype=torch.float32):
         if isinstance(x, torch.Tensor):
@@ -96,6 +113,11 @@ class AdvantageActorCritic(BaseModel):
             return np.empty(0, dtype=np.int32)
         if self._on_kernels(view, feature):
             return self._hip.infer(view, feature)
+        if isinstance(view, torch.Tensor) and view.dtype == torch.bfloat16:
+            # bf16 cells [n, H, W, 8] (channels, zeros, a constant 1) without the bf16 kernels: the channels go back to float32
+            view = view[..., :self.view_space[-1]].float().contiguous()
+            if self._on_kernels(view, feature):
+                return self._hip.infer(view, feature)
         policy, _ = self.net(self._tensor(view), self._tensor(feature))
         acts = torch.multinomial(policy, 1).squeeze(1).to(torch.int32)
         return acts if isinstance(view, torch.Tensor) else acts.cpu().numpy()

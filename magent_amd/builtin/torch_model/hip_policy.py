@@ -1,6 +1,6 @@
 """Binding of the hand-written MI355X inference kernels for the reference's deep Q network (include/magent_policy.h,
 magent_amd/csrc/policy.hip) to the PyTorch model that owns the parameters (dqn.py: _QNet) -- and, further down, of the float32 kernels,
-the recurrent network's (float32 and bf16: one state table, _DrqnPolicy) and the actor-critic's.
+the recurrent network's (float32 and bf16: one state table, _DrqnPolicy) and the actor-critic's (float32 and bf16).
 
 The kernels want every weight matrix in the operand order of v_mfma_f32_32x32x16_bf16 ("fragment order") and every
 activation in the order a lane of the MFMA result holds its 16 outputs ("slot order"); both are plain index permutations of
@@ -485,6 +485,98 @@ class HipA2cPolicyF32(_Packed):
         stream = _stream(dev)
         self._chunked("policy_a2c_infer_f32", n, chunk, lambda beg, m: self._lib.policy_a2c_infer_f32(
             ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
+            self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
+            _ptr(value[beg:] if want_value else None), stream))
+        out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
+        return out if len(out) > 1 else actions
+
+
+class _A2cWeightsBf16(ctypes.Structure):
+    _fields_ = [("dense_view", ctypes.c_void_p), ("dense_view_cells", ctypes.c_void_p), ("dense_emb", ctypes.c_void_p), ("dense", ctypes.c_void_p),
+                ("comm", ctypes.c_void_p * 2), ("head", ctypes.c_void_p), ("dense_view_bias", ctypes.c_void_p),
+                ("dense_emb_bias", ctypes.c_void_p), ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
+
+
+class HipA2cPolicy(_Packed):
+    """one acting step of an _ActorCritic with bf16 matrix operands -- the two input layers (k_a2c_trunk_bf16, from float32 views or from
+    the engine's bf16 cells), dense 512 and the two CommNet steps (k_a2c_layer_bf16, the column sums by k_a2c_colsum_part_bf16 +
+    k_a2c_colsum_bf16), the heads, the softmax and the draw (k_a2c_head_bf16): magent_amd/csrc/policy_a2c_bf16.hip.  Accumulation, biases,
+    relu / tanh, the column sums, the softmax and the draw are float32; the rounding points are listed in include/magent_policy.h.
+
+    The draw, the chunking and the CommNet rule are HipA2cPolicyF32's: without CommNet `chunk` agents per C call, with it the whole call
+    in ONE.  `cells`: whether the shape has a cell entry (view_c <= 7 and 8 H W <= 4096).  `lib`: _Packed."""
+
+    _source = "net"
+
+    def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
+        super().__init__(net, view_space, feature_space, n_action, device, chunk, lib)
+        self.use_comm = net.comm is not None
+        region = self._lib.policy_a2c_supported(ctypes.byref(self.shape))          # (AttributeError: a library without these kernels)
+        if net.dense.in_features != 512 or net.dense.out_features != 512 or not region:
+            raise ValueError("network shape not taken by the HIP bf16 A2C kernels")
+        self.cells = bool(region & 2)
+
+    @torch.no_grad()
+    def pack(self):
+        net, dev, A, s = self.net, self.device, self.shape.n_action, self.shape
+        stamp = _SourceStamp(net)
+        wv = net.dense_view.weight.detach().float()                              # [256][H W C], K in the view's own order
+        t = {
+            "dense_view": fragment_order(_pad_k(wv, (wv.shape[1] + 15) // 16 * 16)),
+            "dense_emb": fragment_order(_pad_k(net.dense_emb.weight.detach().float(), (s.feat + 15) // 16 * 16)),
+            "dense": fragment_order(net.dense.weight.detach().float()),
+            "dense_view_bias": net.dense_view.bias.detach().float().contiguous(),
+            "dense_emb_bias": net.dense_emb.bias.detach().float().contiguous(),
+            "dense_bias": net.dense.bias.detach().float().contiguous(),
+        }
+        if self.cells:        # the cells' order: k = 8 cell + channel, zeros for the channels a cell pads with (and for its constant 1.0)
+            hw = s.view_h * s.view_w
+            wc = wv.new_zeros(256, hw, 8)
+            wc[:, :, :s.view_c] = wv.reshape(256, hw, s.view_c)
+            t["dense_view_cells"] = fragment_order(_pad_k(wc.reshape(256, 8 * hw), (hw + 1) // 2 * 16))
+        head, hb = _head_32x512([(0, net.policy.weight), (A, net.value.weight)], dev, [(0, net.policy.bias), (A, net.value.bias)])
+        t["head"], t["head_bias"] = fragment_order(head), hb
+        w = _A2cWeightsBf16()
+        _set_pointers(w, t)
+        if self.use_comm:
+            for k, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
+                t["comm%d" % k] = fragment_order(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
+                w.comm[k] = t["comm%d" % k].data_ptr()
+        w.use_comm = int(self.use_comm)
+        self._set_packed(t, w, stamp)
+
+    @torch.no_grad()
+    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
+        """view float32 [n][H][W][C] -- or bfloat16 [n][H][W][8], the engine's cells (GridWorld.get_observation_device_bf16), where the
+        shape has them --, feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
+        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
+        probabilities [n][A] and / or the values [n] if asked for"""
+        cells16 = view.dtype == torch.bfloat16
+        s = self.shape
+        assert view.device == feature.device and view.device.type == self.device.type
+        assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32 and view.shape[0] == feature.shape[0]
+        if cells16:
+            if not self.cells:
+                raise ValueError("this view shape has no bf16 cell entry")
+            assert tuple(view.shape[1:]) == (s.view_h, s.view_w, 8)
+        else:
+            assert view.dtype == torch.float32 and tuple(view.shape[1:]) == (s.view_h, s.view_w, s.view_c)
+        entry = "policy_a2c_infer_bf16" if cells16 else "policy_a2c_infer"
+        call = getattr(self._lib, entry)
+        if self.stale():
+            self.pack()
+        n, dev, A = view.shape[0], view.device, s.n_action
+        if u is None:
+            u = torch.rand(n, device=dev)
+        assert u.device == dev and u.dtype == torch.float32 and u.is_contiguous() and u.shape == (n,)
+        actions = torch.empty(n, dtype=torch.int32, device=dev)
+        policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
+        value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
+        chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
+        self._grow_work(dev, self._lib.policy_a2c_workspace_bytes, min(n, chunk), int(self.use_comm))
+        stream = _stream(dev)
+        self._chunked(entry, n, chunk, lambda beg, m: call(
+            ctypes.byref(s), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
             self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
             _ptr(value[beg:] if want_value else None), stream))
         out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())

@@ -43,7 +43,7 @@
 
 namespace {
 
-using namespace magent_amd::f32;      // the vector types, mfma4, relu, and the shared blocks: the dense pair, pingpong, head_gemm512, out_of
+using namespace magent_amd::f32;      // the vector types, mfma4, relu, and the shared blocks: the dense pair, pingpong, head_gemm512, out_of, policy_epilogue
 
 constexpr int HID = 512;
 // ---------------------------------------------------------------------------------------------------- the input layers
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(HID) k_a2c_colsum_f32(const float *part, int n
 }
 
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
-constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES, PH_PITCH = 33;
+constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES, PH_PITCH = POLICY_ROW_PITCH;
 
 struct PHeadArgs {
     const float *h;           // [n][512]
@@ -204,46 +204,8 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
     // lane (agent, g) holds outputs out_of(r, g); its partner lane ^ 32 the other sixteen
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[r] += A.bh[out_of(r, g)];
-    float top = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int o = out_of(r, g);
-        if (o < A.n_action) top = fmaxf(top, acc[r]);            // (a NaN is passed over here and reaches the sum through its own exp)
-    }
-    top = fmaxf(top, __shfl_xor(top, 32));
-    float e[16], sum = 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int o = out_of(r, g);
-        e[r] = o < A.n_action ? expf(acc[r] - top) : 0.0f;
-        sum += e[r];
-    }
-    sum += __shfl_xor(sum, 32);
-    float *row = s_p + (w * 32 + r32) * PH_PITCH;
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-        const int o = out_of(r, g);
-        float p = e[r] / sum;
-        p = p < 1e-10f ? 1e-10f : (p > (float)(1.0 - 1e-10) ? (float)(1.0 - 1e-10) : p);      // torch.clamp: a NaN stays
-        if (o < A.n_action) {
-            row[o] = p;
-            if (live && A.policy) A.policy[(size_t)agent * A.n_action + o] = p;
-        }
-        if (o == A.n_action && live && A.value) A.value[agent] = acc[r];
-    }
-    __syncthreads();
-    if (g == 0 && live) {
-        float c = row[0];
-        for (int a = 1; a < A.n_action; a++) c += row[a];
-        const float t = A.u[agent] * c;
-        int act = A.n_action - 1;                                // (no c_a > t: rounding, or a NaN in the row)
-        c = row[0];
-        for (int a = 0; a < A.n_action - 1; a++) {
-            if (c > t) { act = a; break; }
-            c += row[a + 1];
-        }
-        A.actions[agent] = act;
-    }
+    // softmax, clamp, the stores and the draw: policy_epilogue (policy_f32_dev.h), the bf16 head's too
+    policy_epilogue(acc, g, A.n_action, s_p + (w * 32 + r32) * PH_PITCH, live, agent, A.u, A.actions, A.policy, A.value);
 }
 
 // ---------------------------------------------------------------------------------------------------- the workspace

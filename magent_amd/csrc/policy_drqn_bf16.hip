@@ -51,39 +51,14 @@ using magent_amd::f32::q_epilogue;
 using magent_amd::f32::out_of;
 using magent_amd::f32::sigmoid;
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+using magent_amd::bf16::bf16x8;            // and the streamed-row blocks (policy_bf16_dev.h)
+using magent_amd::bf16::ring3;
+using magent_amd::bf16::round_bf16x8;
 
 constexpr int STATE = 512, GRU_TILES = STATE / 32, KSTEPS = STATE / 16;
 constexpr int GRU_WAVES = 8, GRU_THREADS = 64 * GRU_WAVES, GRU_CHUNK = 2;     // k-steps per register buffer; a wave has three buffers (ring3)
 constexpr int QH_WAVES = 4, QH_THREADS = 64 * QH_WAVES;
 constexpr int XCDS = 8;
-
-// eight float32 (k = 8 g + 0..7 of a k-step) rounded to the MFMA's operand: four v_cvt_pk_bf16_f32 (nearest even; a NaN stays a NaN)
-__device__ __forceinline__ bf16x8 round_bf16x8(const f32x4 &a, const f32x4 &b) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-    u32x4 u;
-    u[0] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{a[0], a[1]}), bf16x2));
-    u[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{a[2], a[3]}), bf16x2));
-    u[2] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{b[0], b[1]}), bf16x2));
-    u[3] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{b[2], b[3]}), bf16x2));
-    return __builtin_bit_cast(bf16x8, u);
-}
-
-// NC chunks of operands through three register buffers: chunk c + 2 loads while chunk c's MFMAs run -- the look-ahead of two ping-pong
-// buffers of twice the size (four k-steps, 12 MFMAs) in three quarters of their registers: with the h half's float32 operands two buffers of
-// four k-steps did not fit 256 VGPRs beside the four accumulators.  Fully unrolled: no branch for the wait counts to merge over.
-template <int NC, class Buf, class Load, class Run>
-__device__ __forceinline__ void ring3(Buf (&op)[3], const Load &load, const Run &run) {
-    load(0, op[0]);
-    load(1, op[1]);
-#pragma unroll
-    for (int c = 0; c < NC; c++) {
-        if (c + 2 < NC) load(c + 2, op[(c + 2) % 3]);
-        run(op[c % 3]);
-    }
-}
 
 struct GruArgs {
     const bf16x8 *x;          // [n][64 units of 8]: the trunk's hidden layer, slot order

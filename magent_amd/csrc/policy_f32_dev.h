@@ -9,8 +9,10 @@
 //   hidden_out with the sinks ToX / ToHid            the 128 agents x 256 outputs dense pair (k_dqn_head_f32, k_a2c_trunk_f32)
 //   head_gemm512                                     the one-wave K = 512, 32-output head GEMM (k_drqn_head_f32, k_a2c_head_f32)
 //   q_epilogue                                       the dueling combination, torch.argmax's pick, the stores (k_dqn_head_f32, k_drqn_head_f32)
+//   policy_epilogue                                  softmax, clamp, the stores and the inverse-CDF draw (k_a2c_head_f32, k_a2c_head_bf16)
 //   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, k_drqn_gru_bf16)
-// policy_drqn_bf16.hip takes out_of, sigmoid, q_epilogue and pingpong from here too (its gates, blend and epilogue are float32).
+// policy_drqn_bf16.hip takes out_of, sigmoid, q_epilogue and pingpong from here too (its gates, blend and epilogue are float32), and
+// policy_a2c_bf16.hip out_of, relu and policy_epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -207,6 +209,56 @@ __device__ __forceinline__ void q_epilogue(const f32x16 &h, int g, int n_action,
 #pragma unroll
             for (int r = 0; r < 16; r++) { const int o = out_of(r, g); if (o < n_action) q[(size_t)agent * n_action + o] = h[r] + shift; }
         }
+    }
+}
+
+// The probability row of a lane pair and its draw (k_a2c_head_f32, k_a2c_head_bf16).  Lane (agent, g) holds the outputs out_of(r, g) of acc
+// = logits + bias (outputs 0..n_action-1) and the value (output n_action); its partner lane ^ 32 the other sixteen.  p = clamp(softmax
+// with the row maximum subtracted, 1e-10, 1 - 1e-10); the row goes through `row` (POLICY_ROW_PITCH floats of LDS per agent, the lane
+// pair's own) to the lane that holds the agent's action 0, which draws: c_0 = p_0, c_a = c_(a-1) + p_a, t = u c_(A-1), the smallest a with
+// c_a > t, else A - 1.  live lanes store p (if policy), the value (if value) and the action.  EVERY wave of the workgroup calls this (a
+// barrier stands between the row's stores and the draw).
+constexpr int POLICY_ROW_PITCH = 33;
+__device__ __forceinline__ void policy_epilogue(const f32x16 &acc, int g, int n_action, float *row, bool live, int agent, const float *u,
+                                                int *actions, float *policy, float *value) {
+    float top = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = out_of(r, g);
+        if (o < n_action) top = fmaxf(top, acc[r]);            // (a NaN is passed over here and reaches the sum through its own exp)
+    }
+    top = fmaxf(top, __shfl_xor(top, 32));
+    float e[16], sum = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = out_of(r, g);
+        e[r] = o < n_action ? expf(acc[r] - top) : 0.0f;
+        sum += e[r];
+    }
+    sum += __shfl_xor(sum, 32);
+#pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int o = out_of(r, g);
+        float p = e[r] / sum;
+        p = p < 1e-10f ? 1e-10f : (p > (float)(1.0 - 1e-10) ? (float)(1.0 - 1e-10) : p);      // torch.clamp: a NaN stays
+        if (o < n_action) {
+            row[o] = p;
+            if (live && policy) policy[(size_t)agent * n_action + o] = p;
+        }
+        if (o == n_action && live && value) value[agent] = acc[r];
+    }
+    __syncthreads();
+    if (g == 0 && live) {
+        float c = row[0];
+        for (int a = 1; a < n_action; a++) c += row[a];
+        const float t = u[agent] * c;
+        int act = n_action - 1;                                // (no c_a > t: rounding, or a NaN in the row)
+        c = row[0];
+        for (int a = 0; a < n_action - 1; a++) {
+            if (c > t) { act = a; break; }
+            c += row[a + 1];
+        }
+        actions[agent] = act;
     }
 }
 

@@ -1,9 +1,11 @@
 """Development helper (GPU box): time of AdvantageActorCritic.infer_action on device observations of the battle shape (13 x 13 x 7, 34
-features, 21 actions), with and without CommNet -- the kernel path (magent_amd/csrc/policy_a2c_f32.hip) against the PyTorch path
-(MAGENT_POLICY_F32=torch: the network's forward pass, then torch.multinomial) of the same network on the same inputs.
+features, 21 actions), with and without CommNet -- the float32 kernel path (magent_amd/csrc/policy_a2c_f32.hip), the opt-in bf16 kernel
+path (infer_dtype="bf16", magent_amd/csrc/policy_a2c_bf16.hip) on the same float32 views and on the engine's bf16 cells of them, and the
+PyTorch path (MAGENT_POLICY_F32=torch: the network's forward pass, then torch.multinomial) of the same network on the same inputs, all in
+one session.
 
 Each size and path: a warm-up of --warm seconds of calls first (code objects load, libraries pick their algorithms, clocks settle), then
-the calls of one timed region behind a synchronize.  Useful FLOP are those of the network's matrix products, 2 K N per layer and agent.
+the calls of one timed region (at least 1000) behind a synchronize.  Useful FLOP are those of the network's matrix products, 2 K N per layer and agent.
 
     python tools/a2c_rate.py [n ...] [--reps R] [--no-torch]"""
 import argparse
@@ -52,7 +54,7 @@ def timed(fn, reps, warm_s):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("sizes", nargs="*", type=int, default=[40000, 131072, 400000])
-    ap.add_argument("--reps", type=int, default=0, help="timed calls per size and path (default: ~3 s of calls, at least 20)")
+    ap.add_argument("--reps", type=int, default=0, help="timed calls per size and path (default: ~3 s of calls, at least 1000)")
     ap.add_argument("--warm", type=float, default=2.0, help="seconds of warm-up calls per size and path")
     ap.add_argument("--no-torch", action="store_true")
     args = ap.parse_args()
@@ -70,22 +72,30 @@ def main():
         del os.environ["MAGENT_POLICY_F32"]
         ref.net.load_state_dict(model.net.state_dict())
         assert ref._hip is None
+        bf16 = AdvantageActorCritic(env, 0, "bf16", use_comm=comm, infer_dtype="bf16")
+        bf16.net.load_state_dict(model.net.state_dict())
+        assert bf16.bf16_kernels, "the bf16 kernel path is not taken"
         per_agent = flops(comm)
         for n in args.sizes:
             g = torch.Generator(device=dev).manual_seed(n)
             view = (torch.rand((n,) + VS, device=dev, generator=g) < 0.3).float()
             feat = torch.rand((n, F), device=dev, generator=g)
+            cells = torch.zeros((n,) + VS[:2] + (8,), dtype=torch.bfloat16, device=dev)       # the engine's cells of the same views
+            cells[..., :VS[2]] = view.to(torch.bfloat16)
+            cells[..., 7] = 1.0
+            assert bf16._on_kernels(cells, feat) and bf16._on_kernels(view, feat) and model._on_kernels(view, feat)
             row = "n %7d  %s" % (n, "CommNet" if comm else "plain  ")
-            for name, m in (("device", model),) + (() if args.no_torch else (("PyTorch", ref),)):
-                call = lambda: m.infer_action((view, feat), None)
+            paths = (("f32 kernels", model, view), ("bf16 kernels, f32 views", bf16, view), ("bf16 kernels, bf16 cells", bf16, cells))
+            for name, m, v in paths + (() if args.no_torch else (("PyTorch", ref, view),)):
+                call = lambda: m.infer_action((v, feat), None)
                 call()
                 torch.cuda.synchronize()
-                reps = args.reps or max(20, int(3.0 / max(1e-4, n * per_agent / (0.3 * PEAK))))
+                reps = args.reps or max(1000, int(3.0 / max(1e-4, n * per_agent / (0.3 * PEAK))))
                 dt = timed(call, reps, args.warm)
-                row += "  %s infer_action %8.3f ms (%d calls) = %5.1f TFLOP/s useful, %.3f of the f32 matrix peak;" % (
+                row += "\n    %-26s infer_action %8.3f ms (%d calls) = %6.1f TFLOP/s useful, %.3f of the f32 matrix peak" % (
                     name, dt * 1e3, reps, n * per_agent / dt / 1e12, n * per_agent / dt / PEAK)
             print(row, flush=True)
-            del view, feat
+            del view, feat, cells
             torch.cuda.empty_cache()
 
 
