@@ -105,6 +105,9 @@ int discrete_snake_add_object(EnvHandle game, int obj_id, int n, const char *met
  * PART 2 -- additive MI355X extensions (device-resident buffers; SURVEY.md 8b "extensions allowed")
  * All pointers below are DEVICE pointers on the environment's device.  Calls enqueue work on the
  * environment's HIP stream and return without waiting; env_sync() waits for the stream.
+ * Observation views come in two formats: float32 [n][view_h][view_w][n_channel], the layout of env_get_observation
+ * (env_get_observation_device, env_cycle_many), and bf16 cells [n][view_h][view_w][8], one 16-byte vector per window cell
+ * (env_get_observation_device_bf16; per entry in env_cycle_many_cells).  Feature rows are float32 in both.
  * ------------------------------------------------------------------------------------------------- */
 
 /* same layout as env_get_observation, written straight into caller-owned device memory */
@@ -141,6 +144,17 @@ int env_step_many(EnvHandle *games, int n, int *done);
  * stream with env_get_stream); the outputs are complete when the call returns (the host has waited for `done`). */
 int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float **feat, const int **actions,
                    float **rewards, int *done, int n_threads);
+/* env_cycle_many with the view format chosen PER ENTRY: view_cells[e * n_group + g] != 0 says that view[e * n_group + g] is a bf16-cell
+ * buffer [n][view_h][view_w][8] in env_get_observation_device_bf16's format (the channels rounded to nearest even, zeros up to channel
+ * 6, 1.0 in channel 7; 16-byte aligned), 0 that it is float32 as in env_cycle_many; view_cells == NULL: every entry is float32 -- that
+ * is env_cycle_many itself, which is this call with NULL.  One side of a game may feed a bf16 network while the other feeds a rule actor
+ * (actor_infer_action_device reads float32 views).  Everything else -- NULL entries, when `actions` are read, what is complete at
+ * return, which of the three forms an environment takes (a cell row is 16 * view_h * view_w bytes: of a packed buffer's segments only the
+ * feature pointer can still miss the 16-byte alignment the batched forms ask for) -- is env_cycle_many's, and so is the number of
+ * launches: a render launch writes every (environment, group) slot in the slot's own format.  A cell entry for a game with more than
+ * 7 channels, or one that is not 16-byte aligned, is FATAL as in env_get_observation_device_bf16. */
+int env_cycle_many_cells(EnvHandle *games, int n_env, int n_group, void **view, const unsigned char *view_cells,
+                         float **feat, const int **actions, float **rewards, int *done, int n_threads);
 /* out[e * n_group + g] = number of agents of group g in environment e (env_get_info "num" for a whole batch; host only) */
 int env_num_many(EnvHandle *games, int n_env, int n_group, int *out);
 /* wait until everything enqueued on the environment's stream has finished */

@@ -353,6 +353,21 @@ __global__ void __launch_bounds__(64 * RENDER_WAVES) k_render_batch(const BatchI
     } else if (it.W.vc_packed) render_block<true, true, 1, true, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
     else render_block<true, true, 1, false, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
 }
+// ... of a call with a bf16-cell entry (env_cycle_many_cells): every slot in its own format (render_block_any)
+__global__ void __launch_bounds__(64 * RENDER_WAVES) k_render_batch_cells(const BatchItem *items, int slots) {
+    const int e = blockIdx.y / slots, k = blockIdx.y - e * slots;
+    const BatchItem &it = items[e];
+    if (k >= it.M.n || (int)blockIdx.x >= it.M.blocks[k]) return;
+    const RenderArgs R = it.M.R[k];
+    const RenderPlan P = it.M.P[k];
+    RenderWorld V;
+    V.w = it.W.w; V.h = it.W.h; V.G = it.W.G; V.viewcell = it.W.viewcell; V.mask = it.W.mask; V.grp = it.W.grp[R.g]; V.type = it.W.type[R.g];
+    if (it.W.turn_mode) {
+        if (it.W.vc_packed) render_block_any<true, true>(V, R, P, blockIdx.x, it.M.blocks[k]);
+        else render_block_any<false, true>(V, R, P, blockIdx.x, it.M.blocks[k]);
+    } else if (it.W.vc_packed) render_block_any<true, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
+    else render_block_any<false, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
+}
 
 // clear_dead for every group of a small world in ONE launch of one workgroup (GridWorld::clear_dead, GridWorld.cc:633-665):
 // stable compaction of the survivors into the alternate buffers + Agent::init_reward + re-indexing of the map (groups with
@@ -414,8 +429,10 @@ void launch_clear_solo_all(hipStream_t s, const WorldView &W, const ClearArgs &A
     const size_t lds = M.vh > 0 ? sizeof(int) * ((size_t)W.G * M.vh * M.vw + W.G) : 0;
     hipLaunchKernelGGL(k_clear_solo_all, dim3(1), dim3(SOLO_THREADS), lds, s, W, A, gtab, ttab, M);
 }
-void launch_cycle_batch(hipStream_t s, const BatchItem *d_items, int n_env, int slots, int max_blocks, size_t render_lds, size_t step_lds) {
-    if (slots > 0 && max_blocks > 0)
+void launch_cycle_batch(hipStream_t s, const BatchItem *d_items, int n_env, int slots, int max_blocks, size_t render_lds, size_t step_lds, bool cells) {
+    if (slots > 0 && max_blocks > 0 && cells)
+        hipLaunchKernelGGL(k_render_batch_cells, dim3(max_blocks, n_env * slots), dim3(64 * RENDER_WAVES), render_lds, s, d_items, slots);
+    else if (slots > 0 && max_blocks > 0)
         hipLaunchKernelGGL(k_render_batch, dim3(max_blocks, n_env * slots), dim3(64 * RENDER_WAVES), render_lds, s, d_items, slots);
     hipLaunchKernelGGL(k_step_solo_batch, dim3(n_env), dim3(SOLO_STEP_THREADS), step_lds, s, d_items);
 }

@@ -10,10 +10,14 @@ namespace magent_amd {
 //   cycle_finish  : the step record, the host mirror of what clear_dead did on the device
 // can this environment's cycle run as the two-launch form (k_render_multi + k_step_solo)?  No device work: the batch asks
 // before it decides whose stream an environment uses
-bool Env::cycle_eligible(int n_group, float *const *view, float *const *feat, int *first_obs_out) {
+// (every cycle of every form asks here first: a bf16-cell entry the engine cannot write is refused here, as observe_device refuses it)
+bool Env::cycle_eligible(int n_group, float *const *view, const unsigned char *cells, float *const *feat, int *first_obs_out) {
     if (!device_ready) fatal("cycle called before reset");
     const int NG = (int)groups.size();
     if (n_group != NG) fatal("env_cycle_many: n_group (%d) differs from the number of groups (%d)", n_group, NG);
+    for (int g = 0; cells && view && g < NG; g++)
+        if (cells[g] && view[g] && (n_channel() > 7 || (((uintptr_t)view[g]) & 15)))
+            fatal("get_observation (bf16 cells): needs at most 7 channels (this game has %d) and a 16-byte aligned buffer", n_channel());
     // (a group given actions twice: the literal loop, by the call sequence)
     // the observed groups must share one minimap (same window, same "skip absorbed" rule) to be rendered by one launch
     return solo_ok(total_agents()) && !step_pending && !serial_calls_on && observed_groups_ok(view, feat, true, false, first_obs_out);
@@ -39,9 +43,9 @@ bool Env::observed_groups_ok(float *const *view, float *const *feat, bool goals_
     return n_obs <= RENDER_MULTI_MAX;
 }
 
-bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, BatchItem &item) {
+bool Env::cycle_prepare(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, BatchItem &item) {
     int first_obs = -1;
-    if (!cycle_eligible(n_group, view, feat, &first_obs)) return false;
+    if (!cycle_eligible(n_group, view, cells, feat, &first_obs)) return false;
     // goals that are given actions may move: the call sequence (set_action_device sends such a step through the literal loop)
     for (int g = 0; actions && g < n_group && g < (int)groups.size(); g++) if (actions[g] && groups[g].type->can_absorb && groups[g].n > 0) return false;
     enter();
@@ -61,6 +65,7 @@ bool Env::cycle_prepare(int n_group, float *const *view, float *const *feat, con
         }
         const int k = M.n++;
         prepare_render(g, W, M.R[k], M.P[k], view[g], feat[g]);
+        M.R[k].cells16 = cells && cells[g] ? 1 : 0;
         M.blocks[k] = M.P[k].spans + M.P[k].feat_blocks;
     }
     // ---- launch 2: set_action, step, get_reward, clear_dead, the next minimap
@@ -110,12 +115,12 @@ void Env::cycle_finish(int *done) {
     after_clear(take_survivors(), cyc_next_mini);
 }
 
-void Env::cycle(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, int *done) {
+void Env::cycle(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, int *done) {
     static thread_local BatchItem item;
-    if (!cycle_prepare(n_group, view, feat, actions, rewards, item)) {   // the general path: the same calls one after the other
+    if (!cycle_prepare(n_group, view, cells, feat, actions, rewards, item)) {   // the general path: the same calls one after the other
         const int NG = (int)groups.size();
         for (int g = 0; g < NG; g++) {
-            if (view && view[g]) observe_device(g, view[g], feat[g]);
+            if (view && view[g]) observe_device(g, view[g], feat[g], cells && cells[g]);
             if (actions && actions[g]) set_action_device(g, actions[g]);
         }
         step(done);
@@ -145,7 +150,7 @@ void Env::cycle(int n_group, float *const *view, float *const *feat, const int *
 // (others: called once the batches' launches are enqueued, with the list of environments that took neither form -- food_mode, rules on the
 // host, generic bodies beyond the one-launch step ...; they keep their own streams and the caller runs their ordinary cycles, on its host
 // threads, while the batches are in flight)
-void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **feat, const int **actions, float **rewards, int *done,
+void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, const unsigned char *cells, float **feat, const int **actions, float **rewards, int *done,
                      const std::function<void(const std::vector<int> &)> &others) {
     // Which form does every environment take?  kind 1: the two-launch cycle (one workgroup steps the world); kind 2: the batched pipeline.
     // A world that could take either goes to the pipeline from `batch_pipe_min` agents on (measured on the MI355X, profiles/r06_summary.md:
@@ -158,7 +163,7 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
     for (int e = 0; e < n_env; e++) {
         const int o = e * n_group;
         envs[e]->batch_width = n_env;      // (solo_ok: the batch's limit; plan_render: the launch is shared)
-        const bool solo = envs[e]->cycle_eligible(n_group, view ? view + o : nullptr, feat ? feat + o : nullptr, nullptr);
+        const bool solo = envs[e]->cycle_eligible(n_group, view ? view + o : nullptr, cells ? cells + o : nullptr, feat ? feat + o : nullptr, nullptr);
         int total = 0;
         const bool pipe = pipe_on && envs[e]->pipe_eligible(n_group, view ? view + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr, &total);
         kind[e] = pipe && (!solo || total >= pipe_min) ? 2 : solo ? 1 : 0;
@@ -192,21 +197,22 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
         // item e describes environment e (an environment that does not take the two-launch cycle leaves a skip marker).  A description costs
         // ~0.2 us of host time (measured: 28 us for 128 environments) -- sharing them out over threads cost more than it saved.
         int slots = 0, max_blocks = 0, n_in = 0;
+        bool any_cells = false;            // (some slot of the launch is written as bf16 cells: the render kernel that takes both formats)
         size_t render_lds = 0, step_lds = 0;
         for (int e = 0; e < n_env; e++) {
             const int o = e * n_group;
             BatchItem &it = lead.batch_h[e];
-            if (kind[e] == 1 && !envs[e]->cycle_prepare(n_group, view ? view + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr,
+            if (kind[e] == 1 && !envs[e]->cycle_prepare(n_group, view ? view + o : nullptr, cells ? cells + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr,
                                                        rewards ? rewards + o : nullptr, it)) kind[e] = 0;
             if (kind[e] != 1) { it.M.n = 0; it.S.rec = nullptr; continue; }
             n_in++;
             slots = std::max(slots, it.M.n);
-            for (int q = 0; q < it.M.n; q++) { max_blocks = std::max(max_blocks, it.M.blocks[q]); render_lds = std::max(render_lds, render_strip_lds(it.M.P[q])); }
+            for (int q = 0; q < it.M.n; q++) { max_blocks = std::max(max_blocks, it.M.blocks[q]); render_lds = std::max(render_lds, render_strip_lds(it.M.P[q])); any_cells |= it.M.R[q].cells16 != 0; }
             step_lds = std::max(step_lds, solo_step_lds(it.W, it.S));
         }
         if (n_in > 0) {
             HIP_OK(hipMemcpyAsync(lead.batch_d, lead.batch_h, sizeof(BatchItem) * (size_t)n_env, hipMemcpyHostToDevice, lead.stream));
-            launch_cycle_batch(lead.stream, lead.batch_d, n_env, slots, max_blocks, render_lds, step_lds);
+            launch_cycle_batch(lead.stream, lead.batch_d, n_env, slots, max_blocks, render_lds, step_lds, any_cells);
             HIP_OK(hipGetLastError());
         }
     }
@@ -254,7 +260,7 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
             if (kind[e] != 2) continue;
             const int o = e * n_group;
             PipeItem &it = lead.pipe_h[piped.size()];
-            envs[e]->pipe_prepare(n_group, view ? view + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr, rewards ? rewards + o : nullptr, it, rounds, sweep_ok);
+            envs[e]->pipe_prepare(n_group, view ? view + o : nullptr, cells ? cells + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr, rewards ? rewards + o : nullptr, it, rounds, sweep_ok);
             it.rec = lead.reports_d + piped.size();
             piped.push_back(e);
             for (int g = 0; g < n_group; g++) PD.max_n = std::max(PD.max_n, it.W.grp[g].n);
@@ -268,6 +274,7 @@ void Env::cycle_many(Env **envs, int n_env, int n_group, float **view, float **f
                 sweep_feat = std::max(sweep_feat, it.M.P[q].feat_blocks);
                 sweep_vhw = std::max(sweep_vhw, it.M.R[q].VH * it.M.R[q].VW);
                 sweep_steps = std::max(sweep_steps, ((long long)it.M.R[q].n * it.M.R[q].VH * it.M.R[q].VW + 63) / 64);
+                PD.cells |= it.M.R[q].cells16;
             }
         }
         PD.n_env = (int)piped.size();
@@ -343,6 +350,8 @@ bool Env::pipe_sweep_ok(float *const *view) {
             if (render_sweep_mini_ok(W, R)) pipe_sweep_shape |= 1 << g;
         }
     }
+    // (a bf16-cell entry of that shape has the sweeping body's cell form, render_sweep2_body<true, ...>: measured over the 64 segments of
+    // 32 x (2 x 2000) it is the faster cell render by 12 % of the round, profiles/batch_cells.md -- the format decides nothing here)
     for (int g = 0; g < (int)groups.size(); g++)
         if (view && view[g] && groups[g].n > 0 && !((pipe_sweep_shape >> g) & 1)) return false;
     return true;
@@ -360,7 +369,7 @@ static long long pipe_own_cells() {
 // clear_dead would do on the host, with the launches left to the batch (launch_pipe_cycle).  Stale state that only the first cycle meets
 // -- the painted map, the first minimap, tables, grown buffers -- is brought up to date by launches of the environment's own, on the
 // batch's stream, ahead of the batch's.
-void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, PipeItem &it, int rounds, bool sweep_ok) {
+void Env::pipe_prepare(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, PipeItem &it, int rounds, bool sweep_ok) {
     enter();
     const int NG = (int)groups.size();
     (void)n_group;
@@ -375,9 +384,10 @@ void Env::pipe_prepare(int n_group, float *const *view, float *const *feat, cons
     it.W = this->view();
     for (int g = 0; g < NG; g++) {
         if (!(view && view[g]) || groups[g].n == 0) continue;
-        if (own_render) { observe_device(g, view[g], feat[g]); continue; }
+        if (own_render) { observe_device(g, view[g], feat[g], cells && cells[g]); continue; }
         const int k = it.M.n++;
         prepare_render(g, it.W, it.M.R[k], it.M.P[k], view[g], feat[g]);
+        it.M.R[k].cells16 = cells && cells[g] ? 1 : 0;
         it.M.blocks[k] = it.M.P[k].spans + it.M.P[k].feat_blocks;
     }
     if (sweep_ok && it.M.n > 0) pipe_sweep_rounds++;

@@ -145,10 +145,11 @@ public:
     void info_device(int g, const char *name, void *out);
     // one environment cycle -- observe + set_action per group, step, rewards, clear_dead (examples/train_battle.py:61-109) --
     // in two launches for small worlds (k_render_multi, k_step_solo); NULL entries skip that call for that group
-    void cycle(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, int *done);
+    // (cells: per group, non-zero where `view` is a bf16-cell buffer as observe_device's cells16 takes it; nullptr: float32 everywhere)
+    void cycle(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, int *done);
     // ... and for many small environments in ONE pair of launches (one workgroup of k_step_solo_batch per environment)
     int group_count(int g) const { return g >= 0 && g < (int)groups.size() ? groups[g].n : 0; }
-    static void cycle_many(Env **envs, int n_env, int n_group, float **view, float **feat, const int **actions, float **rewards, int *done,
+    static void cycle_many(Env **envs, int n_env, int n_group, float **view, const unsigned char *cells, float **feat, const int **actions, float **rewards, int *done,
                            const std::function<void(const std::vector<int> &)> &others);
     void sync();
     void profile_read(const char *name, int *n, float *ms);
@@ -244,15 +245,15 @@ private:
     bool serial_calls_on = false;
     MiniArgs next_minimap();
     int *fold_counts();
-    bool cycle_eligible(int n_group, float *const *view, float *const *feat, int *first_obs_out);
-    bool cycle_prepare(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, BatchItem &item);
+    bool cycle_eligible(int n_group, float *const *view, const unsigned char *cells, float *const *feat, int *first_obs_out);
+    bool cycle_prepare(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, BatchItem &item);
     void cycle_finish(int *done);
     void adopt_stream(Env &lead);
     bool cyc_next_mini = false, cyc_mini_skip = false; int cyc_mini_vh = 0, cyc_mini_vw = 0;
     BatchItem *batch_h = nullptr, *batch_d = nullptr; size_t batch_cap = 0;   // (lead environment of a batch)
     // many environments per launch through the pipeline of plain games (engine_batch.hip: "the pipeline, batched"; pipe.hip)
     bool pipe_eligible(int n_group, float *const *view, float *const *feat, const int *const *actions, int *total_out);
-    void pipe_prepare(int n_group, float *const *view, float *const *feat, const int *const *actions, float *const *rewards, PipeItem &it, int rounds, bool sweep_ok);
+    void pipe_prepare(int n_group, float *const *view, const unsigned char *cells, float *const *feat, const int *const *actions, float *const *rewards, PipeItem &it, int rounds, bool sweep_ok);
     void pipe_after(float *const *rewards, const StepRecord &report, int *done);
     bool pipe_sweep_ok(float *const *view);
     // (lead environment of such a batch) the items, every environment's report on the device and in pinned memory, the last-workgroup ticket

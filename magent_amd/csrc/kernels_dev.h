@@ -355,6 +355,15 @@ __device__ __forceinline__ void render_block(const RenderWorld &W, const RenderA
         }
     }
 }
+// one slot of a batched render launch in whichever format its RenderArgs ask for (k_render_multi_cells, k_render_batch_cells,
+// k_pipe_render_cells: the launches of an env_cycle_many_cells call with a bf16-cell entry -- the format is per (environment, group), so one
+// launch may hold both; the branch is on a scalar, a workgroup takes one side.  A call without a cell entry launches the float32 kernels,
+// which carry none of this)
+template <bool PACKED, bool TURN>
+__device__ __forceinline__ void render_block_any(const RenderWorld &W, const RenderArgs &R, const RenderPlan &P, int bx, int nb) {
+    if (R.cells16) render_block<true, true, 1, PACKED, TURN, true>(W, R, P, bx, nb);
+    else render_block<true, true, 1, PACKED, TURN, false>(W, R, P, bx, nb);
+}
 // ---- the battle-shaped observation, software-pipelined (round 3).
 // Two groups, minimap channels, 7 channels, packed view cells, no turn_mode, 16-byte aligned output: BASELINE's battle / the
 // bench workload.  Same flat cell sequence, same strips, same stores as render_block; what changes is everything in front of them:

@@ -108,7 +108,7 @@ void launch_pend_to_actions(hipStream_t s, const GroupDev &G, const TypeDev &T, 
 void launch_any_real_action(hipStream_t s, const int *actions, int n, const TypeDev &T, const int2 *delta, int *flag);
 void launch_step_report(hipStream_t s, int *counters, StepRecord *rec, int seq, int NG);
 void launch_commit_action(hipStream_t s, const GroupDev &G, const TypeDev &T);
-void launch_cycle_batch(hipStream_t s, const BatchItem *d_items, int n_env, int slots, int max_blocks, size_t render_lds, size_t step_lds);
+void launch_cycle_batch(hipStream_t s, const BatchItem *d_items, int n_env, int slots, int max_blocks, size_t render_lds, size_t step_lds, bool cells);   // cells: some slot is written as bf16 cells
 size_t render_strip_lds(const RenderPlan &P);
 size_t solo_step_lds(const WorldView &W, const SoloStep &S);
 
@@ -228,7 +228,7 @@ struct PipeItem {
 // what the batch's last workgroup does: every environment's report to pinned host memory in one piece, then the word the host waits for
 struct PipeCtl { const StepRecord *reports_d; StepRecord *reports_h; int *ticket; int *flag_h; int flag_seq; int n_env; };
 constexpr int PIPE_REPORT_BYTES = 128;     // of a StepRecord: everything ahead of the tuning marks
-struct PipeDims { int n_env, max_n, max_total, G, slots, render_blocks, rounds, kmax, sweep, hist_cells; size_t render_lds; };
+struct PipeDims { int n_env, max_n, max_total, G, slots, render_blocks, rounds, kmax, sweep, hist_cells; size_t render_lds; int cells; };   // cells: some slot of the render launch is written as bf16 cells
 void launch_pipe_upload(hipStream_t s, const PipeItem *h_items, PipeItem *d_items, int n_env);      // (h_items: pinned, device-visible)
 void launch_pipe_cycle(hipStream_t s, const PipeItem *d_items, const PipeDims &D, const PipeCtl &C);
 bool render_sweep_mini_ok(const WorldView &W, const RenderArgs &R);

@@ -46,6 +46,19 @@ __global__ void __launch_bounds__(64 * RENDER_WAVES) k_pipe_render(const PipeIte
     if (it.W.vc_packed) render_block<true, true, 1, true, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
     else render_block<true, true, 1, false, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
 }
+// ... of a call with a bf16-cell entry (env_cycle_many_cells): every slot in its own format (render_block_any).  FLAT addressing for the
+// reason given above
+__global__ void __launch_bounds__(64 * RENDER_WAVES) k_pipe_render_cells(const PipeItem *__restrict__ items, int slots) {
+    const int e = blockIdx.y / slots, k = blockIdx.y - e * slots;
+    const PipeItem &it = items[e];
+    if (k >= it.M.n || (int)blockIdx.x >= it.M.blocks[k]) return;
+    const RenderArgs R = it.M.R[k];
+    const RenderPlan P = it.M.P[k];
+    RenderWorld V;
+    V.w = it.W.w; V.h = it.W.h; V.G = it.W.G; V.viewcell = it.W.viewcell; V.mask = it.W.mask; V.grp = it.W.grp[R.g]; V.type = it.W.type[R.g];
+    if (it.W.vc_packed) render_block_any<true, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
+    else render_block_any<false, false>(V, R, P, blockIdx.x, it.M.blocks[k]);
+}
 // ... or, when every observed group of the batch has the battle shape [wall | has, hp, minimap | has, hp, minimap] (two groups, packed view
 // cells): the sweeping kernel (render_sweep_dev.h), `sweep` workgroups per (environment, group) segment -- ~256 over the launch, the
 // geometry it has on its own -- + the feature rows' workgroups.  (Round 6 first measured it level with the generic workgroups and left it
@@ -65,6 +78,22 @@ __global__ void __launch_bounds__(64 * RENDER_WAVES) k_pipe_render_sweep(const P
     const RenderPlan P = it.M.P[k];
     const RenderWorld V = pipe_render_world(it, R.g);
     render_sweep2_body<false, 2, 2, true>(V, R, P, sweep, bx, sweep + feat_blocks);
+}
+// ... of a call with a bf16-cell entry: a segment's workgroups write 16-byte cells (render_sweep2_body<true, ...>, what k_render_sweep2 has for
+// a single environment's cells) or float32, as the segment's RenderArgs say
+__global__ void __launch_bounds__(64 * RENDER_WAVES) k_pipe_render_sweep_cells(const PipeItem *__restrict__ items, int slots, int sweep, int segs, int feat_blocks) {
+    int seg, bx;
+    if ((int)blockIdx.x < segs * sweep) { seg = blockIdx.x / sweep; bx = blockIdx.x - seg * sweep; }
+    else { const int f = blockIdx.x - segs * sweep; seg = f / feat_blocks; bx = sweep + (f - seg * feat_blocks); }
+    const int e = seg / slots, k = seg - e * slots;
+    const PipeItem &it = items[e];
+    if (k >= it.M.n) return;
+    RenderArgs R = it.M.R[k];
+    globalize(R);
+    const RenderPlan P = it.M.P[k];
+    const RenderWorld V = pipe_render_world(it, R.g);
+    if (R.cells16) render_sweep2_body<true, 2, 2, true>(V, R, P, sweep, bx, sweep + feat_blocks);
+    else render_sweep2_body<false, 2, 2, true>(V, R, P, sweep, bx, sweep + feat_blocks);
 }
 __global__ void __launch_bounds__(SCAN_THREADS) k_pipe_set_action(const PipeItem *__restrict__ items) {
     PIPE_ITEM();
@@ -185,7 +214,11 @@ static size_t pipe_eval_lds(int kmax) { return (size_t)kmax * 256 * 8; }
 size_t render_sweep_lds(int VHW, int C) { return (size_t)RENDER_WAVES * 2 * 64 * C * sizeof(float) + (size_t)VHW * sizeof(RenderFastPos); }
 void launch_pipe_cycle(hipStream_t s, const PipeItem *d_items, const PipeDims &D, const PipeCtl &C) {
     const dim3 by_agent((D.max_n + 255) / 256, D.G, D.n_env), by_tile((D.max_n + SCAN_TILE - 1) / SCAN_TILE, D.G, D.n_env);
-    if (D.slots > 0 && D.sweep > 0)
+    if (D.slots > 0 && D.sweep > 0 && D.cells)
+        hipLaunchKernelGGL(k_pipe_render_sweep_cells, dim3((D.sweep + D.render_blocks) * D.n_env * D.slots), dim3(64 * RENDER_WAVES), D.render_lds, s, d_items, D.slots, D.sweep, D.n_env * D.slots, std::max(1, D.render_blocks));
+    else if (D.slots > 0 && D.render_blocks > 0 && D.cells)
+        hipLaunchKernelGGL(k_pipe_render_cells, dim3(D.render_blocks, D.n_env * D.slots), dim3(64 * RENDER_WAVES), D.render_lds, s, d_items, D.slots);
+    else if (D.slots > 0 && D.sweep > 0)
         hipLaunchKernelGGL(k_pipe_render_sweep, dim3((D.sweep + D.render_blocks) * D.n_env * D.slots), dim3(64 * RENDER_WAVES), D.render_lds, s, d_items, D.slots, D.sweep, D.n_env * D.slots, std::max(1, D.render_blocks));
     else if (D.slots > 0 && D.render_blocks > 0)
         hipLaunchKernelGGL(k_pipe_render, dim3(D.render_blocks, D.n_env * D.slots), dim3(64 * RENDER_WAVES), D.render_lds, s, d_items, D.slots);

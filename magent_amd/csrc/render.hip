@@ -208,6 +208,15 @@ __global__ void __launch_bounds__(64 * RENDER_WAVES) k_render_multi(WorldView W,
     else render_block<true, true, 1, PACKED, false>(render_world(W, M.R[k].g), M.R[k], M.P[k], blockIdx.x, M.blocks[k]);
 }
 
+// ... with a slot written as bf16 cells (env_cycle_many_cells): every slot in its own format (render_block_any)
+template <bool PACKED>
+__global__ void __launch_bounds__(64 * RENDER_WAVES) k_render_multi_cells(WorldView W, RenderMulti M) {
+    const int k = blockIdx.y;
+    if ((int)blockIdx.x >= M.blocks[k]) return;
+    if (W.turn_mode) render_block_any<PACKED, true>(render_world(W, M.R[k].g), M.R[k], M.P[k], blockIdx.x, M.blocks[k]);
+    else render_block_any<PACKED, false>(render_world(W, M.R[k].g), M.R[k], M.P[k], blockIdx.x, M.blocks[k]);
+}
+
 // the painted map streamed through the caches ahead of the renders of a map that does not fit the L2s (Env::observe_device: when, and why)
 __global__ void __launch_bounds__(256) k_touch(const uint4 *p, size_t n16, unsigned *sink) {
     unsigned acc = 0;
@@ -309,10 +318,14 @@ int launch_render(hipStream_t s, const WorldView &W, const RenderArgs &R, const 
 void launch_render_multi(hipStream_t s, const WorldView &W, const RenderMulti &M) {
     size_t lds = 0;
     int mx = 0;
-    for (int k = 0; k < M.n; k++) { lds = std::max(lds, (size_t)RENDER_WAVES * M.P[k].strip_floats * sizeof(float)); mx = std::max(mx, M.blocks[k]); }
+    bool cells = false;
+    for (int k = 0; k < M.n; k++) { lds = std::max(lds, (size_t)RENDER_WAVES * M.P[k].strip_floats * sizeof(float)); mx = std::max(mx, M.blocks[k]); cells |= M.R[k].cells16 != 0; }
     if (M.n <= 0 || mx <= 0) return;
     dim3 grid(mx, M.n), block(64 * RENDER_WAVES);
-    if (W.vc_packed) hipLaunchKernelGGL((k_render_multi<true>), grid, block, lds, s, W, M);
+    if (cells) {       // (ONE launch whatever the formats of its slots)
+        if (W.vc_packed) hipLaunchKernelGGL((k_render_multi_cells<true>), grid, block, lds, s, W, M);
+        else hipLaunchKernelGGL((k_render_multi_cells<false>), grid, block, lds, s, W, M);
+    } else if (W.vc_packed) hipLaunchKernelGGL((k_render_multi<true>), grid, block, lds, s, W, M);
     else hipLaunchKernelGGL((k_render_multi<false>), grid, block, lds, s, W, M);
 }
 

@@ -128,11 +128,14 @@ int env_step_many(EnvHandle *games, int n, int *done) {
 // clear_dead (the loop body of examples/train_battle.py:61-109) -- for n_env independent environments, driven by
 // n_threads host threads inside the library (no Python GIL, one HIP stream per environment).  Arrays are indexed
 // [e * n_group + g]; a NULL view / actions / rewards entry skips that call for that group.
-int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float **feat, const int **actions,
-                   float **rewards, int *done, int n_threads) {
+// view_cells[e * n_group + g] != 0: that view entry is a bf16-cell buffer (env_get_observation_device_bf16's format); NULL: all float32
+int env_cycle_many_cells(EnvHandle *games, int n_env, int n_group, void **view_any, const unsigned char *view_cells, float **feat, const int **actions,
+                         float **rewards, int *done, int n_threads) {
+    float **view = (float **)view_any;
+    const unsigned char *cells = view ? view_cells : nullptr;
     auto one = [&](int e) {
         const int o = e * n_group;
-        E(games[e])->cycle(n_group, view ? view + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr,
+        E(games[e])->cycle(n_group, view ? view + o : nullptr, cells ? cells + o : nullptr, feat ? feat + o : nullptr, actions ? actions + o : nullptr,
                            rewards ? rewards + o : nullptr, &done[e]);
     };
     // several environments: one pair of launches for all that are small enough (MAGENT_TUNE batch_cycle=0: one by one, by threads)
@@ -140,7 +143,7 @@ int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float
     if (n_env >= 2 && batch) {
         std::vector<Env *> envs(n_env);
         for (int e = 0; e < n_env; e++) envs[e] = E(games[e]);
-        Env::cycle_many(envs.data(), n_env, n_group, view, feat, actions, rewards, done, [&](const std::vector<int> &alone) {
+        Env::cycle_many(envs.data(), n_env, n_group, view, cells, feat, actions, rewards, done, [&](const std::vector<int> &alone) {
             // environments outside the batch: ordinary cycles on their own streams, spread over the host threads
             if (n_threads <= 1 || alone.size() <= 1) { for (int e : alone) one(e); return; }
             cycle_pool().run(n_threads < (int)alone.size() ? n_threads : (int)alone.size(), (int)alone.size(), [&](int k) { one(alone[k]); });
@@ -150,6 +153,10 @@ int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float
     if (n_threads <= 1 || n_env <= 1) { for (int e = 0; e < n_env; e++) one(e); return 0; }
     cycle_pool().run(n_threads < n_env ? n_threads : n_env, n_env, one);
     return 0;
+}
+int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float **feat, const int **actions,
+                   float **rewards, int *done, int n_threads) {
+    return env_cycle_many_cells(games, n_env, n_group, (void **)view, nullptr, feat, actions, rewards, done, n_threads);
 }
 // agent counts of n_env environments x n_group groups in one call (the host mirror: no device work)
 int env_num_many(EnvHandle *games, int n_env, int n_group, int *out) {

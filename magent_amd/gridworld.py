@@ -690,7 +690,20 @@ class EnvBatch(object):
     """Several independent environments on one GPU, cycled together by host threads inside the library.
 
     cycle(views, feats, actions, rewards): per environment and group, observe into the given device tensors, set the
-    device actions, step, fetch rewards, clear_dead -- one library call for the whole batch (env_cycle_many)."""
+    device actions, step, fetch rewards, clear_dead -- one library call for the whole batch (env_cycle_many).
+
+    View formats.  A view entry is float32 [n, H, W, C] or, for games of at most 7 channels, torch.bfloat16 cells [n, H, W, 8] -- what
+    get_observation_device_bf16 writes and the bf16 policies read as they are.  The format is per (environment, group): one side may feed a
+    bf16 network, the other a rule actor, which reads float32 views (env_cycle_many_cells).
+
+    Packed layout.  A policy over a batch wants ONE call for all environments, i.e. each group's rows of all environments in one
+    contiguous tensor; the engine's batched forms want every segment 16-byte aligned (a world whose pointers are not goes through the call
+    sequence, alone).  packed_offsets() places environment e's rows of group g at row sum(round_up(n, 4)) of the environments before it:
+    four rows of any row size that is a multiple of 4 bytes are a multiple of 16 bytes, so cells, float32 views, feature rows, int32
+    actions and float32 rewards all keep the alignment; packed_pointers() turns one base tensor per group into cycle()'s pointer array.  The
+    <= 3 pad rows between two segments are never written by the engine -- the caller fills the buffers once -- and what a policy computes
+    for them is ignored: the engine reads each segment's n actions only.  A network whose rows talk to each other -- the A2C's CommNet
+    averages over all rows of a call -- would average over every environment of a packed buffer: call it per environment, on the segment."""
 
     def __init__(self, envs, n_threads=8):
         self.envs, self.n_threads = list(envs), n_threads
@@ -720,6 +733,49 @@ class EnvBatch(object):
     def _ptrs(self, tensors):
         return tensors if isinstance(tensors, ctypes.Array) else self.pointers(tensors)
 
+    def cell_flags(self, tensors):
+        """the view_cells array of cycle() for a list (per env) of lists (per group) of view tensors: 1 where the tensor is
+        torch.bfloat16 -- bf16 cells [..., H, W, 8] --, 0 for float32 and None; None when no entry is bf16 (the float32 call).  Raises
+        ValueError for a bf16 tensor whose last dimension is not 8 or whose game has more than 7 channels: the engine would abort."""
+        if tensors is None:
+            return None
+        flags, found = (ctypes.c_ubyte * (len(self.envs) * self.n_group))(), False
+        for e, per_env in enumerate(tensors):
+            for g, t in enumerate(per_env):
+                if t is None or str(t.dtype) != "torch.bfloat16":
+                    continue
+                h, w, c = self.envs[e].view_space[g]
+                if c > 7:
+                    raise ValueError("bf16-cell observations hold at most 7 channels; this game has %d (pass a float32 view)" % c)
+                if t.dim() < 3 or tuple(t.shape[-3:]) != (h, w, 8):
+                    raise ValueError("a bf16 view is [..., %d, %d, 8] (one 16-byte cell per window position), not %s" % (h, w, tuple(t.shape)))
+                flags[e * self.n_group + g], found = 1, True
+        return flags if found else None
+
+    def packed_offsets(self, nums=None, align_rows=4):
+        """(offsets[n_env][n_group], totals[n_group]) of the packed layout, in rows: offsets[e][g] = sum over e' < e of nums[e'][g] rounded up
+        to a multiple of align_rows, totals[g] the same sum over all environments (the rows a group's buffers need).  nums: agent counts
+        [env][group], default self.nums_array().  Host arithmetic only.  align_rows=4 keeps every segment of every array 16-byte aligned."""
+        n = np.asarray(self.nums_array() if nums is None else nums, dtype=np.int64).reshape(-1, self.n_group)
+        padded = (n + align_rows - 1) // align_rows * align_rows
+        ends = np.cumsum(padded, axis=0)
+        return ends - padded, ends[-1] if len(ends) else np.zeros(self.n_group, dtype=np.int64)
+
+    def packed_pointers(self, bases, offsets):
+        """the pointers()-style array of a packed layout: entry [e][g] = bases[g].data_ptr() + offsets[e][g] * (bytes of one row of bases[g]);
+        bases: one contiguous CUDA tensor per group, rows first, or None (every entry of that group NULL).  One data_ptr() call per group."""
+        off = np.asarray(offsets, dtype=np.int64).reshape(len(self.envs), self.n_group)
+        addr = np.zeros(off.shape, dtype=np.uint64)
+        for g, t in enumerate(bases):
+            if t is None:
+                continue
+            row_bytes = (t.numel() // t.shape[0] if t.shape[0] else int(np.prod(t.shape[1:], dtype=np.int64))) * t.element_size()
+            assert t.is_contiguous() and t.data_ptr() % 16 == 0 and row_bytes % 4 == 0, "packed buffers start 16-byte aligned and have rows of a multiple of 4 bytes"
+            addr[:, g] = np.uint64(t.data_ptr()) + (off[:, g] * row_bytes).astype(np.uint64)
+        arr = (ctypes.c_void_p * addr.size)()
+        ctypes.memmove(arr, addr.ctypes.data, addr.nbytes)
+        return arr
+
     def nums(self):
         """agent counts [env][group] (host mirror, no device work)"""
         return self.nums_array().tolist()
@@ -733,9 +789,11 @@ class EnvBatch(object):
         self._lib.env_num_many(self._handles, len(self.envs), self.n_group, self._nums_c)
         return self._nums
 
-    def cycle(self, views=None, feats=None, actions=None, rewards=None):
+    def cycle(self, views=None, feats=None, actions=None, rewards=None, view_cells=None):
         """each argument: list (per env) of lists (per group) of CUDA tensors or None, or the result of pointers();
-        returns the done flags.
+        returns the done flags.  views as nested lists: a torch.bfloat16 tensor [..., H, W, 8] is written as bf16 cells, a float32 one
+        as float32 (ValueError for a bf16 tensor of another shape, or of a game with more than 7 channels).  views as a pointer array:
+        view_cells is cell_flags()'s array for the same tensors, or None when every entry is float32.
 
         Stream contract.  Outputs: the call returns after the host has seen every environment's step record, which the step
         kernel publishes behind an agent-scope release and a workgroup barrier -- rewards, observations and the compacted state
@@ -743,10 +801,12 @@ class EnvBatch(object):
         measured: an event pair per cycle costs a 4000-agent world 30 us of its 110).  Inputs: the library reads `actions` on
         the environments' own streams; with `order_streams` (default on) those streams are first ordered after torch's current
         stream, the producer of the actions, stream to stream.  Callers that synchronise themselves switch it off."""
+        if not isinstance(views, ctypes.Array):      # (ahead of everything else: a refused tensor raises before the library is entered)
+            view_cells = self.cell_flags(views)
         if self.order_streams:
             for e in self._distinct():
                 e.order_after_torch()
-        return self._cycle_raw(views, feats, actions, rewards)
+        return self._cycle_raw(views, feats, actions, rewards, view_cells)
 
     def _distinct(self):
         """one environment per distinct engine stream.  Batched environments share their leader's stream, and an environment may join
@@ -765,9 +825,13 @@ class EnvBatch(object):
             self._uniq, self._uniq_key = uniq, key
         return self._uniq
 
-    def _cycle_raw(self, views, feats, actions, rewards):
-        self._lib.env_cycle_many(self._handles, len(self.envs), self.n_group, self._ptrs(views), self._ptrs(feats),
-                                 self._ptrs(actions), self._ptrs(rewards), self._done, self.n_threads)
+    def _cycle_raw(self, views, feats, actions, rewards, view_cells=None):
+        if view_cells is None:     # (no cell entry: the float32 entry, as ever)
+            self._lib.env_cycle_many(self._handles, len(self.envs), self.n_group, self._ptrs(views), self._ptrs(feats),
+                                     self._ptrs(actions), self._ptrs(rewards), self._done, self.n_threads)
+        else:
+            self._lib.env_cycle_many_cells(self._handles, len(self.envs), self.n_group, self._ptrs(views), view_cells, self._ptrs(feats),
+                                           self._ptrs(actions), self._ptrs(rewards), self._done, self.n_threads)
         if not self._adopted:      # environments cycled together share the first one's stream from now on
             self._adopted = True
             self._uniq_key = None
