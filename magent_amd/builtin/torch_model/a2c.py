@@ -72,22 +72,10 @@ class AdvantageActorCritic(BaseModel):
         # then goes through the bf16 MFMA kernels (magent_amd/csrc/policy_a2c_bf16.hip: bf16 matrix operands and inter-layer rows, float32
         # accumulation, biases, column sums, softmax and draw) where the shape is theirs, and through what "f32" would use where it is not.
         # `bf16_kernels` says which.  Training is untouched by it.
-        self.infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
-        if self.infer_dtype not in ("f32", "bf16"):
-            raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (self.infer_dtype,))
-        self._hip, self.bf16_kernels = None, False
-        if self.device.type == "cuda":
-            from . import hip_policy
-            kinds = [hip_policy.HipA2cPolicy] if self.infer_dtype == "bf16" else []
-            if os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
-                kinds.append(hip_policy.HipA2cPolicyF32)
-            for kind in kinds:
-                try:
-                    self._hip = kind(self.net, self.view_space, self.feature_space, self.num_actions, self.device)
-                    self.bf16_kernels = kind is hip_policy.HipA2cPolicy
-                    break
-                except (ValueError, OSError, AttributeError):
-                    self._hip = None
+        from . import hip_policy
+        self.infer_dtype, self._hip, self.bf16_kernels = hip_policy.acting_policy(
+            infer_dtype, self.device, hip_policy.HipA2cPolicy, hip_policy.HipA2cPolicyF32, self.net, self.view_space, self.feature_space,
+            self.num_actions, self.device)
 
     def _on_kernels(self, view, feature):
         n = len(view)

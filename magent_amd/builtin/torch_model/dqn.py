@@ -95,23 +95,14 @@ class DeepQNetwork(BaseModel):
         # when the network has the reference's default shape.  How far that is from the f32 network on real observations is pinned
         # in tests/test_policy.py::test_bf16_policy_against_the_f32_network (|dQ| <= 2 % of max |Q|, >= 97 % equal greedy actions).
         # Training is float32 either way.
-        self.infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
-        if self.infer_dtype not in ("f32", "bf16"):
-            raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (self.infer_dtype,))
         # "f32" on the GPU goes through hand-written kernels too since round 6: the same float32 arithmetic -- inputs, weights, activations,
         # accumulation -- on the f32 matrix instruction (magent_amd/csrc/policy_f32.hip; tests/test_policy.py pins it to the PyTorch network
         # within float32 round-off).  MAGENT_POLICY_F32=torch keeps the PyTorch / MIOpen forward pass (A/B runs, bench.py's comparison).
-        self._hip = None
-        if self.device.type == "cuda":
-            try:
-                if self.infer_dtype == "bf16":
-                    from .hip_policy import HipDqnPolicy
-                    self._hip = HipDqnPolicy(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
-                elif os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
-                    from .hip_policy import HipDqnPolicyF32
-                    self._hip = HipDqnPolicyF32(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
-            except (ValueError, OSError, AttributeError):
-                self._hip = None
+        # A "bf16" model whose shape the bf16 kernels do not take acts through the PyTorch network, not through the f32 kernels.
+        from . import hip_policy
+        self.infer_dtype, self._hip, _ = hip_policy.acting_policy(
+            infer_dtype, self.device, hip_policy.HipDqnPolicy, hip_policy.HipDqnPolicyF32, self.qnet, self.view_space, self.feature_space,
+            self.num_actions, self.device, f32_after_bf16=False)
         # replay memory; mask == 0 marks the padding transition that closes an unfinished episode (dqn.py:249-252)
         self.memory_size, self.replay_len = memory_size, 0
         d = self.device

@@ -76,22 +76,10 @@ class DeepRecurrentQNetwork(BaseModel):
         # through the bf16 MFMA kernels (magent_amd/csrc/policy_drqn_bf16.hip: bf16 matrix operands, float32 accumulation, gates, blend and
         # states) where the shape is theirs, and through what "f32" would use where it is not.  `bf16_kernels` says which.  Training is
         # untouched by it.
-        self.infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
-        if self.infer_dtype not in ("f32", "bf16"):
-            raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (self.infer_dtype,))
-        self._hip, self.bf16_kernels = None, False
-        if self.device.type == "cuda":
-            from . import hip_policy
-            kinds = [hip_policy.HipDrqnPolicy] if self.infer_dtype == "bf16" else []
-            if os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
-                kinds.append(hip_policy.HipDrqnPolicyF32)
-            for kind in kinds:
-                try:
-                    self._hip = kind(self.qnet, self.view_space, self.feature_space, self.num_actions, self.device)
-                    self.bf16_kernels = kind is hip_policy.HipDrqnPolicy
-                    break
-                except (ValueError, OSError, AttributeError):
-                    self._hip = None
+        from . import hip_policy
+        self.infer_dtype, self._hip, self.bf16_kernels = hip_policy.acting_policy(
+            infer_dtype, self.device, hip_policy.HipDrqnPolicy, hip_policy.HipDrqnPolicyF32, self.qnet, self.view_space, self.feature_space,
+            self.num_actions, self.device)
         # episodes: (views, features, actions, rewards, terminals) as device tensors; the oldest fall out (drqn.py:129-131)
         self.memory_size = memory_size
         self.replay_buffer = collections.deque(maxlen=memory_size)

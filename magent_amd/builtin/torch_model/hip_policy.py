@@ -8,6 +8,7 @@ the torch parameters, done here with tensor ops on the device whenever the param
 parameter was written or replaced since it packed (_SourceStamp), whoever did it -- train(), load(), load_state_dict, an optimiser of
 the caller's.  Setting `.dirty = True` forces a repack."""
 import ctypes
+import os
 
 import torch
 
@@ -25,7 +26,7 @@ class _Weights(ctypes.Structure):
 
 
 def slot_channels(device):
-    """channel (output) held in slot s of a 32-wide tile: (s & 3) + 8 ((s & 15) >> 2) + 4 (s >> 4)  (policy.hip: ch_of)"""
+    """channel (output) held in slot s of a 32-wide tile: (s & 3) + 8 ((s & 15) >> 2) + 4 (s >> 4)  (policy_f32_dev.h: out_of)"""
     s = torch.arange(32, device=device)
     return (s & 3) + 8 * ((s & 15) >> 2) + 4 * (s >> 4)
 
@@ -105,6 +106,27 @@ class _Packed(object):
                 raise RuntimeError("%s failed (%d)" % (name, rc))
 
 
+def acting_policy(infer_dtype, device, bf16_class, f32_class, *args, f32_after_bf16=True):
+    """what a model's constructor needs to act through the kernels: (infer_dtype, policy or None, bf16_kernels).
+    infer_dtype: the argument, else MAGENT_POLICY_DTYPE, else "f32"; validated.  On a CUDA device the policy is the first of bf16_class
+    (asked for by "bf16") and f32_class (unless MAGENT_POLICY_F32=torch; behind the bf16 class only if f32_after_bf16) whose constructor
+    takes `args`: an unsupported shape (ValueError) or a library without these kernels (OSError, AttributeError) passes to the next;
+    None: the PyTorch network acts.  bf16_kernels: the policy is the bf16 class's."""
+    infer_dtype = (infer_dtype or os.environ.get("MAGENT_POLICY_DTYPE", "f32")).lower()
+    if infer_dtype not in ("f32", "bf16"):
+        raise ValueError("infer_dtype must be 'f32' or 'bf16', not %r" % (infer_dtype,))
+    kinds = [bf16_class] if infer_dtype == "bf16" else []
+    if (f32_after_bf16 or not kinds) and os.environ.get("MAGENT_POLICY_F32", "hip").lower() != "torch":
+        kinds.append(f32_class)
+    if torch.device(device).type == "cuda":
+        for kind in kinds:
+            try:
+                return infer_dtype, kind(*args), kind is bf16_class
+            except (ValueError, OSError, AttributeError):
+                pass
+    return infer_dtype, None, False
+
+
 def _stream(device):
     """torch's current stream on a CUDA device; None (the null stream) for the emulated library's CPU tensors"""
     return torch.cuda.current_stream(device).cuda_stream if device.type == "cuda" else None
@@ -134,17 +156,22 @@ def _pad_k(w, k):
     return torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], dim=1) if w.shape[1] < k else w
 
 
+def _conv1_cells(q, c):
+    """conv1 of a trunk as [32][ky][kx][8], K = tap * 8 + channel: the C channels padded to a cell's 8, the bias as the weight of channel 7
+    of tap 0 (the kernels feed a constant 1.0 there: the MFMA adds the bias)"""
+    w1 = q.conv1.weight.detach().float()                              # [32][C][3][3]
+    w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
+    w1[:, 0, 0, 7] = q.conv1.bias.detach().float()
+    return w1
+
+
 def _trunk_bf16(q, shape, dev):
     """conv1, conv2, dense_view, dense_emb of a _QNet / _RecurrentQNet (the same trunk) in bf16 fragment order with their biases in slot
     order, and `hidden`: the hidden unit held in each of the 512 hidden slots (the order the kernels keep the hidden layer in)"""
     ch = slot_channels(dev)
-    c = shape.view_c
     k_dense = (shape.view_h - 4) * (shape.view_w - 4) * 32
-    w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
-    w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
-    w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
     # the kernel pairs the taps (0|3) (1|4) (2|5) (6|7) (8|pad) into its five k-steps (policy.hip: k_dqn_conv)
-    w1 = _pad_k(w1.reshape(32, 72), 80).reshape(32, 10, 8)[:, CONV1_TAP_ORDER].reshape(32, 80)
+    w1 = _pad_k(_conv1_cells(q, shape.view_c).reshape(32, 72), 80).reshape(32, 10, 8)[:, CONV1_TAP_ORDER].reshape(32, 80)
     w2 = q.conv2.weight.detach().float()[:, ch].permute(0, 2, 3, 1).reshape(32, 288)            # K = tap * 32 + slot
     wv = q.dense_view.weight.detach().float().reshape(256, -1, 32)[:, :, ch].reshape(256, k_dense)   # K = position * 32 + slot
     fk = (shape.feat + 15) // 16 * 16
@@ -159,26 +186,54 @@ def _trunk_bf16(q, shape, dev):
     }, hidden
 
 
-class HipDqnPolicy(_Packed):
-    """greedy actions (and, for tests, the Q values) of a dueling conv _QNet, computed by k_dqn_conv + k_dqn_head"""
+class _DqnPolicy(_Packed):
+    """what the two DQN policies share: the constructor's check, the head around a packed trunk and the chunked step.  A subclass names
+    its entries of the library (`_abi`: supported, act_bytes, the entry named in errors, the kernels named in errors) and gives pack() /
+    infer()."""
+    _abi = None
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072):
         super().__init__(qnet, view_space, feature_space, n_action, device, chunk)
-        if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_supported(ctypes.byref(self.shape)):
-            raise ValueError("network shape not taken by the HIP policy kernels")
+        if not (qnet.use_conv and qnet.use_dueling) or not getattr(self._lib, self._abi[0])(ctypes.byref(self.shape)):
+            raise ValueError("network shape not taken by the %s" % self._abi[3])
         self.k_dense = (view_space[0] - 4) * (view_space[1] - 4) * 32
 
-    @torch.no_grad()
-    def pack(self):
-        q, dev = self.qnet, self.device
-        stamp = _SourceStamp(q)
-        t, hidden = _trunk_bf16(q, self.shape, dev)
-        head, _ = _head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], dev)
-        t["head"] = fragment_order(head[:, hidden])
+    def _pack_head(self, t, stamp, frag, hidden=None):
+        """the dueling head into `t` (a packed trunk; hidden: the hidden unit in each position of the kernels' hidden layer, None: natural
+        order) and the whole into the library's struct"""
+        q = self.qnet
+        head, _ = _head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], self.device)
+        t["head"] = frag(head if hidden is None else head[:, hidden])
         w = _Weights()
         _set_pointers(w, t)
         w.value_bias = float(q.value.bias.detach().float().item())
         self._set_packed(t, w, stamp)
+
+    def _step(self, entry, view, feature, want_q):
+        """the library's `entry` on every chunk of the call"""
+        call = getattr(self._lib, entry)
+        if self.stale():
+            self.pack()
+        n = view.shape[0]
+        actions = torch.empty(n, dtype=torch.int32, device=view.device)
+        q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=view.device) if want_q else None
+        self._grow_work(view.device, getattr(self._lib, self._abi[1]), min(n, self.chunk))      # (activations in the kernels' own layout + the conv kernel's dump line)
+        stream = _stream(view.device)
+        self._chunked(self._abi[2], n, self.chunk, lambda beg, m: call(
+            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, self._work.data_ptr(),
+            actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
+        return (actions, q) if want_q else actions
+
+
+class HipDqnPolicy(_DqnPolicy):
+    """greedy actions (and, for tests, the Q values) of a dueling conv _QNet, computed by k_dqn_conv + k_dqn_head"""
+    _abi = ("policy_dqn_supported", "policy_dqn_act_bytes", "policy_dqn_infer", "HIP policy kernels")
+
+    @torch.no_grad()
+    def pack(self):
+        stamp = _SourceStamp(self.qnet)
+        t, hidden = _trunk_bf16(self.qnet, self.shape, self.device)
+        self._pack_head(t, stamp, fragment_order, hidden)
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -187,18 +242,7 @@ class HipDqnPolicy(_Packed):
         cells16 = view.dtype == torch.bfloat16
         assert view.is_cuda and view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32
         assert (cells16 and view.shape[-1] == 8) or (view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c)
-        call = self._lib.policy_dqn_infer_bf16 if cells16 else self._lib.policy_dqn_infer
-        if self.stale():
-            self.pack()
-        n = view.shape[0]
-        actions = torch.empty(n, dtype=torch.int32, device=view.device)
-        q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=view.device) if want_q else None
-        self._grow_work(view.device, self._lib.policy_dqn_act_bytes, min(n, self.chunk))       # (activations in the kernels' own layout + the conv kernel's dump line)
-        stream = _stream(view.device)
-        self._chunked("policy_dqn_infer", n, self.chunk, lambda beg, m: call(
-            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, self._work.data_ptr(),
-            actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
-        return (actions, q) if want_q else actions
+        return self._step("policy_dqn_infer_bf16" if cells16 else "policy_dqn_infer", view, feature, want_q)
 
 
 # ---------------------------------------------------------------------------------------------------- float32 (the reference's arithmetic)
@@ -212,10 +256,7 @@ def fragment_order_f32(w):
 
 def _trunk_f32(q, shape, dev):
     """conv1, conv2, dense_view, dense_emb of a _QNet / _RecurrentQNet (the same trunk) in f32 fragment order, with their biases"""
-    c = shape.view_c
-    w1 = q.conv1.weight.detach().float()                              # [32][C][3][3] -> [32][ky][kx][8] -> K = tap * 8 + channel
-    w1 = torch.cat([w1, w1.new_zeros(32, 8 - c, 3, 3)], dim=1).permute(0, 2, 3, 1).contiguous()
-    w1[:, 0, 0, 7] = q.conv1.bias.detach().float()       # the kernel feeds a constant 1.0 in channel 7: the MFMA adds the bias
+    w1 = _conv1_cells(q, shape.view_c)
     w2 = q.conv2.weight.detach().float().permute(0, 2, 3, 1).reshape(32, 288)                      # K = tap * 32 + channel
     wv = q.dense_view.weight.detach().float()                                                      # K = position * 32 + channel (NHWC flatten)
     fk = (shape.feat + 7) // 8 * 8
@@ -229,26 +270,15 @@ def _trunk_f32(q, shape, dev):
     }
 
 
-class HipDqnPolicyF32(_Packed):
+class HipDqnPolicyF32(_DqnPolicy):
     """greedy actions (and the Q values) of a dueling conv _QNet in float32 -- inputs, weights, activations, accumulation: the reference
     network's own arithmetic -- computed by k_dqn_conv_f32 + k_dqn_head_f32 on v_mfma_f32_32x32x2_f32 (magent_amd/csrc/policy_f32.hip)"""
-
-    def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072):
-        super().__init__(qnet, view_space, feature_space, n_action, device, chunk)
-        if not (qnet.use_conv and qnet.use_dueling) or not self._lib.policy_dqn_f32_supported(ctypes.byref(self.shape)):
-            raise ValueError("network shape not taken by the HIP f32 policy kernels")
-        self.k_dense = (view_space[0] - 4) * (view_space[1] - 4) * 32
+    _abi = ("policy_dqn_f32_supported", "policy_dqn_f32_act_bytes", "policy_dqn_infer_f32", "HIP f32 policy kernels")
 
     @torch.no_grad()
     def pack(self):
-        q, dev = self.qnet, self.device
-        stamp = _SourceStamp(q)
-        t = _trunk_f32(q, self.shape, dev)
-        t["head"] = fragment_order_f32(_head_32x512([(0, q.advantage.weight), (self.shape.n_action, q.value.weight)], dev)[0])
-        w = _Weights()
-        _set_pointers(w, t)
-        w.value_bias = float(q.value.bias.detach().float().item())
-        self._set_packed(t, w, stamp)
+        stamp = _SourceStamp(self.qnet)
+        self._pack_head(_trunk_f32(self.qnet, self.shape, self.device), stamp, fragment_order_f32)
 
     @torch.no_grad()
     def infer(self, view, feature, want_q=False):
@@ -256,17 +286,7 @@ class HipDqnPolicyF32(_Packed):
         Returns int32 actions [n] (and Q [n][A])"""
         assert view.is_cuda and view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
         assert view.shape[-1] == self.shape.view_c
-        if self.stale():
-            self.pack()
-        n = view.shape[0]
-        actions = torch.empty(n, dtype=torch.int32, device=view.device)
-        q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=view.device) if want_q else None
-        self._grow_work(view.device, self._lib.policy_dqn_f32_act_bytes, min(n, self.chunk))
-        stream = _stream(view.device)
-        self._chunked("policy_dqn_infer_f32", n, self.chunk, lambda beg, m: self._lib.policy_dqn_infer_f32(
-            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, self._work.data_ptr(),
-            actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
-        return (actions, q) if want_q else actions
+        return self._step("policy_dqn_infer_f32", view, feature, want_q)
 
 
 # ---------------------------------------------------------------------------------------------------- the recurrent network (drqn.py)
@@ -421,56 +441,64 @@ class _A2cWeights(ctypes.Structure):
                 ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
 
 
-class HipA2cPolicyF32(_Packed):
-    """one acting step of an _ActorCritic in float32 -- the two input layers (k_a2c_trunk_f32), dense 512 and the two CommNet steps
-    (k_a2c_layer_f32, the column sums by k_a2c_colsum_part_f32 + k_a2c_colsum_f32), the policy and value heads, the softmax and the draw
-    (k_a2c_head_f32): magent_amd/csrc/policy_a2c_f32.hip.
+class _A2cWeightsBf16(ctypes.Structure):
+    _fields_ = [("dense_view", ctypes.c_void_p), ("dense_view_cells", ctypes.c_void_p), ("dense_emb", ctypes.c_void_p), ("dense", ctypes.c_void_p),
+                ("comm", ctypes.c_void_p * 2), ("head", ctypes.c_void_p), ("dense_view_bias", ctypes.c_void_p),
+                ("dense_emb_bias", ctypes.c_void_p), ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
+
+
+class _A2cPolicy(_Packed):
+    """what the two A2C policies share: the constructor's check, the packing of the dense layers, the CommNet steps and the heads, and the
+    chunked step.  A subclass names its entries of the library (`_abi`: supported, workspace_bytes, the kernels named in errors) and its
+    struct (`_struct`) and gives pack() / infer().
 
     The draw is the inverse CDF of one uniform number per agent (include/magent_policy.h: policy_a2c_infer_f32).  Without CommNet a call
     of n agents goes to the kernels `chunk` agents at a time (every agent's row is its own).  With CommNet the mean of the other agents
     spans the call, so the whole n goes to ONE C call whatever `chunk` is: the column sums are then taken over the same blocks of agents
     in the same order, and the result does not depend on `chunk`.  `lib`: _Packed."""
-
     _source = "net"
+    _abi = _struct = None
 
     def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
         super().__init__(net, view_space, feature_space, n_action, device, chunk, lib)
         self.use_comm = net.comm is not None
-        if net.dense.in_features != 512 or net.dense.out_features != 512 or not self._lib.policy_a2c_f32_supported(ctypes.byref(self.shape)):
-            raise ValueError("network shape not taken by the HIP f32 A2C kernels")
+        region = getattr(self._lib, self._abi[0])(ctypes.byref(self.shape))        # (AttributeError: a library without these kernels)
+        if net.dense.in_features != 512 or net.dense.out_features != 512 or not region:
+            raise ValueError("network shape not taken by the HIP %s A2C kernels" % self._abi[2])
+        self.cells = bool(region & 2)          # (a bf16 cell entry: bit 2 of the bf16 kernels' region, never of the f32 kernels')
 
-    @torch.no_grad()
-    def pack(self):
+    def _pack_dense(self, frag, k_multiple, extra=None):
+        """the whole network in `frag` order with K padded to `k_multiple`; extra(t, wv): a subclass's further entries of the struct"""
         net, dev, A = self.net, self.device, self.shape.n_action
         stamp = _SourceStamp(net)
-        wv = net.dense_view.weight.detach().float()
+        up = lambda k: (k + k_multiple - 1) // k_multiple * k_multiple
+        wv = net.dense_view.weight.detach().float()                              # [256][H W C], K in the view's own order
         t = {
-            "dense_view": fragment_order_f32(_pad_k(wv, (wv.shape[1] + 7) // 8 * 8)),
-            "dense_emb": fragment_order_f32(_pad_k(net.dense_emb.weight.detach().float(), (self.shape.feat + 7) // 8 * 8)),
-            "dense": fragment_order_f32(net.dense.weight.detach().float()),
+            "dense_view": frag(_pad_k(wv, up(wv.shape[1]))),
+            "dense_emb": frag(_pad_k(net.dense_emb.weight.detach().float(), up(self.shape.feat))),
+            "dense": frag(net.dense.weight.detach().float()),
             "dense_view_bias": net.dense_view.bias.detach().float().contiguous(),
             "dense_emb_bias": net.dense_emb.bias.detach().float().contiguous(),
             "dense_bias": net.dense.bias.detach().float().contiguous(),
         }
+        if extra is not None:
+            extra(t, wv)
         head, hb = _head_32x512([(0, net.policy.weight), (A, net.value.weight)], dev, [(0, net.policy.bias), (A, net.value.bias)])
-        t["head"], t["head_bias"] = fragment_order_f32(head), hb
-        w = _A2cWeights()
+        t["head"], t["head_bias"] = frag(head), hb
+        w = self._struct()
         _set_pointers(w, t)
         if self.use_comm:
-            for s, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
-                t["comm%d" % s] = fragment_order_f32(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
-                w.comm[s] = t["comm%d" % s].data_ptr()
+            for k, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
+                t["comm%d" % k] = frag(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
+                w.comm[k] = t["comm%d" % k].data_ptr()
         w.use_comm = int(self.use_comm)
         self._set_packed(t, w, stamp)
 
-    @torch.no_grad()
-    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
-        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
-        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
-        probabilities [n][A] and / or the values [n] if asked for"""
+    def _step(self, entry, view, feature, u, want_policy, want_value):
+        """the library's `entry` on every chunk of the call (CommNet: on the whole call)"""
         assert view.device == feature.device and view.device.type == self.device.type
-        assert view.is_contiguous() and feature.is_contiguous() and view.dtype == torch.float32 and feature.dtype == torch.float32
-        assert tuple(view.shape[1:]) == (self.shape.view_h, self.shape.view_w, self.shape.view_c) and view.shape[0] == feature.shape[0]
+        assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32 and view.shape[0] == feature.shape[0]
+        call = getattr(self._lib, entry)
         if self.stale():
             self.pack()
         n, dev, A = view.shape[0], view.device, self.shape.n_action
@@ -481,9 +509,9 @@ class HipA2cPolicyF32(_Packed):
         policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
         value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
         chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
-        self._grow_work(dev, self._lib.policy_a2c_f32_workspace_bytes, min(n, chunk), int(self.use_comm))
+        self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, chunk), int(self.use_comm))
         stream = _stream(dev)
-        self._chunked("policy_a2c_infer_f32", n, chunk, lambda beg, m: self._lib.policy_a2c_infer_f32(
+        self._chunked(entry, n, chunk, lambda beg, m: call(
             ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
             self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
             _ptr(value[beg:] if want_value else None), stream))
@@ -491,59 +519,46 @@ class HipA2cPolicyF32(_Packed):
         return out if len(out) > 1 else actions
 
 
-class _A2cWeightsBf16(ctypes.Structure):
-    _fields_ = [("dense_view", ctypes.c_void_p), ("dense_view_cells", ctypes.c_void_p), ("dense_emb", ctypes.c_void_p), ("dense", ctypes.c_void_p),
-                ("comm", ctypes.c_void_p * 2), ("head", ctypes.c_void_p), ("dense_view_bias", ctypes.c_void_p),
-                ("dense_emb_bias", ctypes.c_void_p), ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
+class HipA2cPolicyF32(_A2cPolicy):
+    """one acting step of an _ActorCritic in float32 -- the two input layers (k_a2c_trunk_f32), dense 512 and the two CommNet steps
+    (k_a2c_layer_f32, the column sums by k_a2c_colsum_part_f32 + k_a2c_colsum_f32), the policy and value heads, the softmax and the draw
+    (k_a2c_head_f32): magent_amd/csrc/policy_a2c_f32.hip.  The draw, the chunking and the CommNet rule: _A2cPolicy."""
+    _abi, _struct = ("policy_a2c_f32_supported", "policy_a2c_f32_workspace_bytes", "f32"), _A2cWeights
+
+    @torch.no_grad()
+    def pack(self):
+        self._pack_dense(fragment_order_f32, 8)
+
+    @torch.no_grad()
+    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
+        """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
+        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
+        probabilities [n][A] and / or the values [n] if asked for"""
+        assert view.dtype == torch.float32 and tuple(view.shape[1:]) == (self.shape.view_h, self.shape.view_w, self.shape.view_c)
+        return self._step("policy_a2c_infer_f32", view, feature, u, want_policy, want_value)
 
 
-class HipA2cPolicy(_Packed):
+class HipA2cPolicy(_A2cPolicy):
     """one acting step of an _ActorCritic with bf16 matrix operands -- the two input layers (k_a2c_trunk_bf16, from float32 views or from
     the engine's bf16 cells), dense 512 and the two CommNet steps (k_a2c_layer_bf16, the column sums by k_a2c_colsum_part_bf16 +
     k_a2c_colsum_bf16), the heads, the softmax and the draw (k_a2c_head_bf16): magent_amd/csrc/policy_a2c_bf16.hip.  Accumulation, biases,
     relu / tanh, the column sums, the softmax and the draw are float32; the rounding points are listed in include/magent_policy.h.
 
-    The draw, the chunking and the CommNet rule are HipA2cPolicyF32's: without CommNet `chunk` agents per C call, with it the whole call
-    in ONE.  `cells`: whether the shape has a cell entry (view_c <= 7 and 8 H W <= 4096).  `lib`: _Packed."""
+    The draw, the chunking and the CommNet rule: _A2cPolicy.  `cells`: whether the shape has a cell entry (view_c <= 7 and 8 H W <= 4096)."""
+    _abi, _struct = ("policy_a2c_supported", "policy_a2c_workspace_bytes", "bf16"), _A2cWeightsBf16
 
-    _source = "net"
-
-    def __init__(self, net, view_space, feature_space, n_action, device, chunk=131072, lib=None):
-        super().__init__(net, view_space, feature_space, n_action, device, chunk, lib)
-        self.use_comm = net.comm is not None
-        region = self._lib.policy_a2c_supported(ctypes.byref(self.shape))          # (AttributeError: a library without these kernels)
-        if net.dense.in_features != 512 or net.dense.out_features != 512 or not region:
-            raise ValueError("network shape not taken by the HIP bf16 A2C kernels")
-        self.cells = bool(region & 2)
-
-    @torch.no_grad()
-    def pack(self):
-        net, dev, A, s = self.net, self.device, self.shape.n_action, self.shape
-        stamp = _SourceStamp(net)
-        wv = net.dense_view.weight.detach().float()                              # [256][H W C], K in the view's own order
-        t = {
-            "dense_view": fragment_order(_pad_k(wv, (wv.shape[1] + 15) // 16 * 16)),
-            "dense_emb": fragment_order(_pad_k(net.dense_emb.weight.detach().float(), (s.feat + 15) // 16 * 16)),
-            "dense": fragment_order(net.dense.weight.detach().float()),
-            "dense_view_bias": net.dense_view.bias.detach().float().contiguous(),
-            "dense_emb_bias": net.dense_emb.bias.detach().float().contiguous(),
-            "dense_bias": net.dense.bias.detach().float().contiguous(),
-        }
-        if self.cells:        # the cells' order: k = 8 cell + channel, zeros for the channels a cell pads with (and for its constant 1.0)
+    def _pack_cells(self, t, wv):
+        """dense_view in the cells' order: k = 8 cell + channel, zeros for the channels a cell pads with (and for its constant 1.0)"""
+        s = self.shape
+        if self.cells:
             hw = s.view_h * s.view_w
             wc = wv.new_zeros(256, hw, 8)
             wc[:, :, :s.view_c] = wv.reshape(256, hw, s.view_c)
             t["dense_view_cells"] = fragment_order(_pad_k(wc.reshape(256, 8 * hw), (hw + 1) // 2 * 16))
-        head, hb = _head_32x512([(0, net.policy.weight), (A, net.value.weight)], dev, [(0, net.policy.bias), (A, net.value.bias)])
-        t["head"], t["head_bias"] = fragment_order(head), hb
-        w = _A2cWeightsBf16()
-        _set_pointers(w, t)
-        if self.use_comm:
-            for k, step in enumerate(net.comm):         # K = the others' mean (C), then the agent's own units (H)
-                t["comm%d" % k] = fragment_order(torch.cat([step.C.weight.detach().float(), step.H.weight.detach().float()], dim=1))
-                w.comm[k] = t["comm%d" % k].data_ptr()
-        w.use_comm = int(self.use_comm)
-        self._set_packed(t, w, stamp)
+
+    @torch.no_grad()
+    def pack(self):
+        self._pack_dense(fragment_order, 16, self._pack_cells)
 
     @torch.no_grad()
     def infer(self, view, feature, u=None, want_policy=False, want_value=False):
@@ -551,33 +566,11 @@ class HipA2cPolicy(_Packed):
         shape has them --, feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
         torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
         probabilities [n][A] and / or the values [n] if asked for"""
-        cells16 = view.dtype == torch.bfloat16
-        s = self.shape
-        assert view.device == feature.device and view.device.type == self.device.type
-        assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32 and view.shape[0] == feature.shape[0]
+        cells16, s = view.dtype == torch.bfloat16, self.shape
         if cells16:
             if not self.cells:
                 raise ValueError("this view shape has no bf16 cell entry")
             assert tuple(view.shape[1:]) == (s.view_h, s.view_w, 8)
         else:
             assert view.dtype == torch.float32 and tuple(view.shape[1:]) == (s.view_h, s.view_w, s.view_c)
-        entry = "policy_a2c_infer_bf16" if cells16 else "policy_a2c_infer"
-        call = getattr(self._lib, entry)
-        if self.stale():
-            self.pack()
-        n, dev, A = view.shape[0], view.device, s.n_action
-        if u is None:
-            u = torch.rand(n, device=dev)
-        assert u.device == dev and u.dtype == torch.float32 and u.is_contiguous() and u.shape == (n,)
-        actions = torch.empty(n, dtype=torch.int32, device=dev)
-        policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
-        value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
-        chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
-        self._grow_work(dev, self._lib.policy_a2c_workspace_bytes, min(n, chunk), int(self.use_comm))
-        stream = _stream(dev)
-        self._chunked(entry, n, chunk, lambda beg, m: call(
-            ctypes.byref(s), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
-            self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
-            _ptr(value[beg:] if want_value else None), stream))
-        out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
-        return out if len(out) > 1 else actions
+        return self._step("policy_a2c_infer_bf16" if cells16 else "policy_a2c_infer", view, feature, u, want_policy, want_value)

@@ -17,7 +17,7 @@
 //   tiles of both layers live in REGISTERS for the life of the wave (92 VGPRs), so an MFMA costs one 16-byte LDS read per
 //   lane.  The weights are the first MFMA operand: the result tile then has the output channels down the registers and the
 //   positions across the lanes, i.e. a lane owns 16 channels of ONE position and stores them as two 16-byte vectors.
-//   (Which 16: ch_of() below.  Activations are kept in that "slot" order; the next layer's weights are permuted to match when
+//   (Which 16: policy_f32_dev.h: out_of().  Activations are kept in that "slot" order; the next layer's weights are permuted to match when
 //   they are packed -- magent_amd/builtin/torch_model/hip_policy.py.)
 // k_dqn_head : dense 2592 -> 256 as a GEMM over 128 agents per workgroup of 8 waves (activations through LDS, packed weights
 //   straight from L2 in fragment order, both streams four K-chunks ahead in registers), the feature embedding, the dueling head
@@ -41,12 +41,15 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// result register r of lane group g (= lane >> 5) is row (r & 3) + 8 (r >> 2) + 4 g of the 32 x 32 tile
-__device__ __forceinline__ int ch_of(int g, int r) { return (r & 3) + 8 * (r >> 2) + 4 * g; }
+// policy_bf16_dev.h: the operand type and the pair conversion.  policy_f32_dev.h: the float32 vector types, relu, q_before, and out_of --
+// result register r of lane group g (= lane >> 5) is row out_of(r, g) of the 32 x 32 tile.
+using magent_amd::bf16::bf16x8;
+using magent_amd::bf16::round_bf16x2;
+using magent_amd::f32::f32x16;
+using magent_amd::f32::f32x4;
+using magent_amd::f32::out_of;
+using magent_amd::f32::q_before;
+using magent_amd::f32::relu;
 
 // conv2's output, dense_view's input: [group of ACT_GROUP agents][K-chunk of 64 values = two positions][agent][64 values].  A k_dqn_head
 // workgroup (ACT_GROUP agents) then reads one contiguous 16 KB block per K-chunk, and its blocks follow each other -- round 2 kept
@@ -73,17 +76,7 @@ struct ConvArgs {
 // +0), then v_cvt_pk_bf16_f32 (round to nearest even; a NaN stays a NaN -- MI355X_MICROARCH.md).  Three instructions per pair.  (Until
 // the non-finite contract, DESIGN.md 3.15, the relu was v_pk_max_i16 against 0 on the rounded pair: two instructions, but a NaN with its sign
 // bit set -- the reference's 0/0 of an empty group's minimap -- is a negative int16 and came out as 0; `fmaxf` makes any NaN a 0.)
-__device__ __forceinline__ unsigned relu_bf16x2(float a, float b) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    const f32x2 v = {__builtin_elementwise_maximum(a, 0.0f), __builtin_elementwise_maximum(b, 0.0f)};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-// torch.argmax's order of a Q row: a NaN above everything (the first NaN wins), then the larger value, the lower index among equals.  Does
-// (v, o) come before (best, arg)?
-__device__ __forceinline__ bool q_before(float v, int o, float best, int arg) {
-    return v != v ? (best == best || o < arg) : (best == best && (v > best || (v == best && o < arg)));
-}
+__device__ __forceinline__ unsigned relu_bf16x2(float a, float b) { return round_bf16x2(relu(a), relu(b)); }
 __device__ __forceinline__ bf16x8 relu_bf16x8(const f32x16 &acc, int base) {
     typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
     u32x4 u;
@@ -538,13 +531,13 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
 #pragma unroll 4
         for (int s = 16; s < 32; s++) h = __builtin_amdgcn_mfma_f32_32x32x16_bf16(s_wh[s * 64 + l], s_hid[hid_at(hagent, 2 * (s - 16) + g)], h, 0, 0, 0);
         const int agent = hagent;
-        // lane (agent, g) holds outputs ch_of(g, r); its partner lane ^ 32 the other sixteen.  The action is the argmax of the Q row
+        // lane (agent, g) holds outputs out_of(r, g); its partner lane ^ 32 the other sixteen.  The action is the argmax of the Q row
         // itself, h + shift, in torch.argmax's order (q_before): a NaN reaches the row, then its first NaN is chosen, as the PyTorch path
         // chooses it; every action lies in [0, n_action) whatever the input
         float sum = 0.0f, value = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int o = ch_of(g, r);
+            const int o = out_of(r, g);
             if (o < A.n_action) sum += h[r];
             if (o == A.n_action) value = h[r];
         }
@@ -555,7 +548,7 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
         int arg = A.n_action;         // (not an action: every output of the row comes before it)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int o = ch_of(g, r);
+            const int o = out_of(r, g);
             if (o < A.n_action && q_before(h[r] + shift, o, best, arg)) { best = h[r] + shift; arg = o; }
         }
         const float obest = __shfl_xor(best, 32);
@@ -565,7 +558,7 @@ __global__ void __launch_bounds__(HEAD_THREADS) k_dqn_head(HeadArgs A) {
             if (g == 0) A.actions[a0 + agent] = arg;
             if (A.q) {
 #pragma unroll
-                for (int r = 0; r < 16; r++) { const int o = ch_of(g, r); if (o < A.n_action) A.q[(size_t)(a0 + agent) * A.n_action + o] = h[r] + shift; }
+                for (int r = 0; r < 16; r++) { const int o = out_of(r, g); if (o < A.n_action) A.q[(size_t)(a0 + agent) * A.n_action + o] = h[r] + shift; }
             }
         }
     }

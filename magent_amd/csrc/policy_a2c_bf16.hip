@@ -29,11 +29,14 @@
 //   is zeros.  The features are float[n][F], rounded the same way.  Two register buffers of two k-steps (K is a run-time number here).
 // k_a2c_layer_bf16<COMM> : [n] x [512] over K = 512 (<false>: h = relu(x Wd^T + bd)) or K = 1024 (<true>: one CommNet step as ONE GEMM,
 //   [others | h] against [C_s | H_s]; others is formed from the stored row and the column sums -- in LDS -- as the operand is fed; the
-//   skip row and tanh in the epilogue).  Three register buffers of two k-steps (policy_bf16_dev.h: ring3).
-// k_a2c_colsum_part_bf16 + k_a2c_colsum_bf16 : the f32 path's column sums over the bf16 rows, added in float32 -- partial sums over
-//   blocks of 256 agents in agent order, then the blocks in block order.  No atomics: the sums are a function of the call's inputs alone.
-// k_a2c_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512, float32 biases, then policy_f32_dev.h: policy_epilogue, the f32
-//   head's own softmax, clamp and draw.
+//   skip row and tanh in the epilogue).  Three register buffers of two k-steps (policy_bf16_dev.h: ring3).  Both GEMM kernels take
+//   their (tile group, agent group) from policy_bf16_dev.h: xcd_place, and their grid from xcd_grid.
+// k_a2c_colsum_part_bf16 + k_a2c_colsum_bf16 : the f32 path's column sums (policy_f32_dev.h: colsum_part, colsum_blocks) over the bf16
+//   rows, added in float32 -- partial sums over blocks of 256 agents in agent order, then the blocks in block order.  No atomics: the
+//   sums are a function of the call's inputs alone.
+// k_a2c_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512 (policy_bf16_dev.h: head_gemm512_bf16, shared with
+//   k_drqn_head_bf16; the operand as stored), float32 biases, then policy_f32_dev.h: policy_epilogue, the f32 head's own softmax, clamp
+//   and draw.  The workspace layout is policy_host.h: a2c_layout, the f32 path's with 2-byte row elements.
 //
 // Whole waves exit early (the head's stay for its barrier); lanes past n repeat the last agent (their own columns of the MFMA, never stored).
 // NaN contract: relu is IEEE maximum, tanhf keeps a NaN, the roundings keep a NaN; without CommNet a NaN or Inf in an
@@ -51,43 +54,16 @@
 
 namespace {
 
-using magent_amd::bf16::bf16x8;
-using magent_amd::bf16::ring3;
-using magent_amd::bf16::round_bf16x8;
-using magent_amd::f32::f32x16;
-using magent_amd::f32::f32x4;
+using namespace magent_amd::bf16;         // the vector types, the conversions, xcd_place / xcd_grid, ring3, head_gemm512_bf16
 using magent_amd::f32::out_of;
-using magent_amd::f32::pingpong;
 using magent_amd::f32::policy_epilogue;
 using magent_amd::f32::POLICY_ROW_PITCH;
 using magent_amd::f32::relu;
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef unsigned short bf16_t;           // a stored bf16 value (rows are addressed by element)
 
-constexpr int HID = 512, KSTEPS = HID / 16, XCDS = 8;
+constexpr int HID = magent_amd::A2C_HID, KSTEPS = HID / 16;
 constexpr int GEMM_WAVES = 8, GEMM_THREADS = 64 * GEMM_WAVES, GEMM_TILES = 4;      // a wave: 32 agents x 4 output tiles; a workgroup: 256 agents
-
-// the two bf16 values of a 32-bit word as float32 (exact), and four float32 rounded to four stored bf16 (nearest even; a NaN stays a NaN)
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ f32x4 widen(const u32x2 &w) { return f32x4{bf_lo(w[0]), bf_hi(w[0]), bf_lo(w[1]), bf_hi(w[1])}; }
-__device__ __forceinline__ u32x2 round_bf16x4(const f32x4 &v) {
-    typedef __attribute__((ext_vector_type(2))) float f32x2;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    u32x2 u;
-    u[0] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{v[0], v[1]}), bf16x2));
-    u[1] = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2{v[2], v[3]}), bf16x2));
-    return u;
-}
-// workgroup L runs on XCD L % 8; the j = L / 8 -th workgroup of an XCD is tile group j % TG of the XCD's (j / TG)-th agent group
-__device__ __forceinline__ void place(int TG, int &tg, int &group) {
-    const int j = blockIdx.x / XCDS;
-    tg = j % TG;
-    group = (j / TG) * XCDS + blockIdx.x % XCDS;
-}
-static unsigned gemm_grid(int groups, int TG) { return (unsigned)((groups + XCDS - 1) / XCDS * XCDS * TG); }
 
 // ---------------------------------------------------------------------------------------------------- the input layers
 constexpr int TR_TG = 256 / 32 / GEMM_TILES, TR_CHUNK = 2;      // two tile groups per half of x; k-steps per register buffer
@@ -104,8 +80,6 @@ struct TrunkArgs {
     int F, FS;                // features and their k-steps
     bf16_t *x;                // [n][512] relu(dense_view) || relu(dense_emb), bf16
 };
-
-struct F8 { f32x4 a[2]; };    // the eight float32 of a lane's half k-step, rounded when they are used
 
 // acc[t] += over `ksteps` k-steps: the lane's operand of k-step s is conv(aload(s)); (k-step s, tile t) of the weights at wp[(s * 8 + t) * 64].
 // aload takes any s up to ksteps (it clamps its addresses).  The next two k-steps load while the current two's 8 MFMAs run.
@@ -171,7 +145,7 @@ template <bool CELLS>
 __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_trunk_bf16(TrunkArgs A) {
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, g = l >> 5, r32 = l & 31;
     int tg, group;
-    place(TR_TG, tg, group);
+    xcd_place(TR_TG, tg, group);
     const int tile0 = (group * GEMM_WAVES + w) * 32;
     if (group >= A.groups || tile0 >= A.n) return;               // (whole waves: the MFMAs below see every lane)
     const int agent = min(tile0 + r32, A.n - 1);
@@ -194,14 +168,14 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_trunk_bf16(TrunkArgs A) {
     } else {
         const float *row = (const float *)A.view + (size_t)agent * A.K;
         trunk_rows<F8>(acc, wvp, A.KS, [&](int s) { return load_f8(row, 16 * s + 8 * g, A.K); },
-                       [](const F8 &v) { return round_bf16x8(v.a[0], v.a[1]); });
+                       [](const F8 &v) { return round_bf16x8(v); });
     }
     trunk_out(acc, A.bv + 32 * T0, orow, g, live);
 #pragma unroll
     for (int t = 0; t < GEMM_TILES; t++) acc[t] = f32x16{0};
     const float *frow = A.feat + (size_t)agent * A.F;
     trunk_rows<F8>(acc, A.we + (size_t)T0 * 64 + l, A.FS, [&](int s) { return load_f8(frow, 16 * s + 8 * g, A.F); },
-                   [](const F8 &v) { return round_bf16x8(v.a[0], v.a[1]); });
+                   [](const F8 &v) { return round_bf16x8(v); });
     trunk_out(acc, A.be + 32 * T0, orow + 256, g, live);
 }
 
@@ -229,7 +203,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
     }
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, g = l >> 5, r32 = l & 31;
     int tg, group;
-    place(LY_TG, tg, group);
+    xcd_place(LY_TG, tg, group);
     const int tile0 = (group * GEMM_WAVES + w) * 32;
     if (group >= A.groups || tile0 >= A.n) return;               // (whole waves: the MFMAs below see every lane)
     const int agent = min(tile0 + r32, A.n - 1);
@@ -294,23 +268,10 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------- column sums in a fixed order
-constexpr int CS_BLOCK = 256;      // agents of a partial sum: block b is agents 256 b .. 256 b + 255 of the call
-
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_bf16(const bf16_t *h, int n, float *part) {
-    const int c = threadIdx.x, beg = blockIdx.x * CS_BLOCK, end = min(beg + CS_BLOCK, n);
-    float s = 0.0f;
-#pragma unroll 16
-    for (int a = beg; a < end; a++) s += bf_lo(h[(size_t)a * HID + c]);
-    part[(size_t)blockIdx.x * HID + c] = s;
+__global__ void __launch_bounds__(HID) k_a2c_colsum_part_bf16(const bf16_t *h, int n, float *part) {      // policy_f32_dev.h: colsum_part
+    magent_amd::f32::colsum_part(n, part, [&](size_t i) { return bf_lo(h[i]); });
 }
-
-__global__ void __launch_bounds__(HID) k_a2c_colsum_bf16(const float *part, int n_blocks, float *sum) {
-    const int c = threadIdx.x;
-    float s = 0.0f;
-#pragma unroll 32
-    for (int b = 0; b < n_blocks; b++) s += part[(size_t)b * HID + c];
-    sum[c] = s;
-}
+__global__ void __launch_bounds__(HID) k_a2c_colsum_bf16(const float *part, int n_blocks, float *sum) { magent_amd::f32::colsum_blocks(part, n_blocks, sum); }
 
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
 constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES;
@@ -332,24 +293,8 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_bf16(PHeadArgs A) {
     const int tile0 = (blockIdx.x * PH_WAVES + w) * 32;
     const int agent = min(tile0 + r32, A.n - 1);                 // (waves past n repeat the last agent and store nothing)
     const bool live = tile0 + r32 < A.n;
-    const bf16x8 *xp = A.h + (size_t)agent * (HID / 8) + g;
-    f32x16 acc = {0};
-    // the operands of the next two k-steps load while the current two's MFMAs run
-    struct Op { bf16x8 a, w; };
-    Op op[2][2];
-    auto load = [&](int c, Op (&d)[2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int s = 2 * c + k;
-            d[k].a = xp[2 * s];
-            d[k].w = A.wh[s * 64 + l];
-        }
-    };
-    auto run = [&](const Op (&d)[2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 2; k++) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d[k].w, d[k].a, acc, 0, 0, 0);
-    };
-    pingpong<KSTEPS / 2>(op, load, run);
+    const bf16x8 *xp = A.h + (size_t)agent * (HID / 8) + g;                   // k-step s: xp[2 s], the operand as stored
+    f32x16 acc = head_gemm512_bf16(A.wh, l, [&](int s) { return xp[2 * s]; }, [](const bf16x8 &v) { return v; });
     // lane (agent, g) holds outputs out_of(r, g); its partner lane ^ 32 the other sixteen
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[r] += A.bh[out_of(r, g)];
@@ -357,19 +302,7 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_bf16(PHeadArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------- the workspace
-struct Layout { size_t x, h0, h1, part, sum, bytes; int n_blocks; };
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-static Layout layout(int n, bool comm) {
-    Layout L{};
-    const size_t rows = up256((size_t)n * HID * sizeof(bf16_t));
-    L.n_blocks = (n + CS_BLOCK - 1) / CS_BLOCK;
-    L.x = 0; L.h0 = rows; L.bytes = 2 * rows;
-    if (comm) {
-        L.h1 = L.bytes; L.part = L.h1 + rows; L.sum = L.part + up256((size_t)L.n_blocks * HID * sizeof(float));
-        L.bytes = L.sum + HID * sizeof(float);
-    }
-    return L;
-}
+static magent_amd::A2cLayout layout(int n, bool comm) { return magent_amd::a2c_layout(n, comm, sizeof(bf16_t)); }      // policy_host.h
 
 static bool cells_supported(const PolicyDqnShape *s) { return s->view_c <= 7 && 8LL * s->view_h * s->view_w <= TR_KMAX; }
 
@@ -387,7 +320,7 @@ static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const v
     hipStream_t st = (hipStream_t)stream;
     magent_amd::StreamDevice on(st);
     if (!on.ok) return 2;
-    const Layout L = layout(n, comm);
+    const magent_amd::A2cLayout L = layout(n, comm);
     char *ws = (char *)workspace;
     bf16_t *x = (bf16_t *)(ws + L.x), *h0 = (bf16_t *)(ws + L.h0);
     const int groups = (n + 32 * GEMM_WAVES - 1) / (32 * GEMM_WAVES);
@@ -396,9 +329,9 @@ static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const v
     T.bv = w->dense_view_bias; T.be = w->dense_emb_bias; T.n = n; T.groups = groups;
     T.K = s->view_h * s->view_w * s->view_c; T.HW = s->view_h * s->view_w; T.KS = cells ? (T.HW + 1) / 2 : (T.K + 15) / 16;
     T.F = s->feat; T.FS = (s->feat + 15) / 16; T.x = x;
-    if (cells) hipLaunchKernelGGL(k_a2c_trunk_bf16<true>, dim3(gemm_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
-    else hipLaunchKernelGGL(k_a2c_trunk_bf16<false>, dim3(gemm_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
-    const dim3 lgrid(gemm_grid(groups, LY_TG));
+    if (cells) hipLaunchKernelGGL(k_a2c_trunk_bf16<true>, dim3(xcd_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
+    else hipLaunchKernelGGL(k_a2c_trunk_bf16<false>, dim3(xcd_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
+    const dim3 lgrid(xcd_grid(groups, LY_TG));
     LayerArgs D{};
     D.in = (const bf16x8 *)x; D.w = (const bf16x8 *)w->dense; D.bias = w->dense_bias; D.out = h0; D.n = n; D.groups = groups;
     hipLaunchKernelGGL(k_a2c_layer_bf16<false>, lgrid, dim3(GEMM_THREADS), 0, st, D);

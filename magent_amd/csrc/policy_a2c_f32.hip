@@ -25,7 +25,8 @@
 //   driver k_drqn_gru_f32 uses), from L2 / HBM.
 // k_a2c_colsum_part_f32 + k_a2c_colsum_f32 : the CommNet column sums without float atomics -- partial sums over blocks of 256 agents (block
 //   b: agents 256 b .. 256 b + 255 of the call, added in agent order), then the blocks added in block order.  The sums are a function of
-//   the call's inputs alone.
+//   the call's inputs alone.  The bodies are policy_f32_dev.h: colsum_part / colsum_blocks, the bf16 path's too; the workspace layout is
+//   policy_host.h: a2c_layout, the bf16 path's too.
 // k_a2c_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 (head_gemm512; outputs 0..A-1 the policy's, output A the value's), softmax with the
 //   row maximum subtracted, clamp, and the draw by the lane that holds the agent's action 0 (the row goes through LDS: a lane pair holds it).
 //
@@ -45,7 +46,7 @@ namespace {
 
 using namespace magent_amd::f32;      // the vector types, mfma4, relu, and the shared blocks: the dense pair, pingpong, head_gemm512, out_of, policy_epilogue
 
-constexpr int HID = 512;
+constexpr int HID = magent_amd::A2C_HID;
 // ---------------------------------------------------------------------------------------------------- the input layers
 constexpr int TR_THREADS = DENSE_THREADS, TR_M = DENSE_M, TR_KC = DENSE_KC, TR_ABUF = DENSE_ABUF;      // the shared dense pair's workgroup (policy_f32_dev.h)
 constexpr int TR_FMAX = 64;                                          // most features (padded to 8)
@@ -162,23 +163,10 @@ __global__ void __launch_bounds__(LY_THREADS) k_a2c_layer_f32(LayerArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------- column sums in a fixed order
-constexpr int CS_BLOCK = 256;      // agents of a partial sum: block b is agents 256 b .. 256 b + 255 of the call
-
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_f32(const float *h, int n, float *part) {
-    const int c = threadIdx.x, beg = blockIdx.x * CS_BLOCK, end = min(beg + CS_BLOCK, n);
-    float s = 0.0f;
-#pragma unroll 16
-    for (int a = beg; a < end; a++) s += h[(size_t)a * HID + c];
-    part[(size_t)blockIdx.x * HID + c] = s;
+__global__ void __launch_bounds__(HID) k_a2c_colsum_part_f32(const float *h, int n, float *part) {      // policy_f32_dev.h: colsum_part
+    colsum_part(n, part, [&](size_t i) { return h[i]; });
 }
-
-__global__ void __launch_bounds__(HID) k_a2c_colsum_f32(const float *part, int n_blocks, float *sum) {
-    const int c = threadIdx.x;
-    float s = 0.0f;
-#pragma unroll 32
-    for (int b = 0; b < n_blocks; b++) s += part[(size_t)b * HID + c];
-    sum[c] = s;
-}
+__global__ void __launch_bounds__(HID) k_a2c_colsum_f32(const float *part, int n_blocks, float *sum) { colsum_blocks(part, n_blocks, sum); }
 
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
 constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES, PH_PITCH = POLICY_ROW_PITCH;
@@ -209,19 +197,7 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------- the workspace
-struct Layout { size_t x, h0, h1, part, sum, bytes; int n_blocks; };
-static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-static Layout layout(int n, bool comm) {
-    Layout L{};
-    const size_t rows = up256((size_t)n * HID * sizeof(float));
-    L.n_blocks = (n + CS_BLOCK - 1) / CS_BLOCK;
-    L.x = 0; L.h0 = rows; L.bytes = 2 * rows;
-    if (comm) {
-        L.h1 = L.bytes; L.part = L.h1 + rows; L.sum = L.part + up256((size_t)L.n_blocks * HID * sizeof(float));
-        L.bytes = L.sum + HID * sizeof(float);
-    }
-    return L;
-}
+static magent_amd::A2cLayout layout(int n, bool comm) { return magent_amd::a2c_layout(n, comm, sizeof(float)); }      // policy_host.h
 
 }  // namespace
 
@@ -251,7 +227,7 @@ int policy_a2c_infer_f32(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, 
     magent_amd::StreamDevice on(st);
     static magent_amd::LdsAllowance lds_ok;
     if (!on.ok || !lds_ok.grant(on.dev, {{reinterpret_cast<const void *>(k_a2c_trunk_f32), (int)TR_LDS}})) return 2;
-    const Layout L = layout(n, comm);
+    const magent_amd::A2cLayout L = layout(n, comm);
     char *ws = (char *)workspace;
     float *x = (float *)(ws + L.x), *h0 = (float *)(ws + L.h0);
     TrunkArgs T{};

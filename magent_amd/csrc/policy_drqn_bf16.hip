@@ -25,10 +25,12 @@
 //   Work split: a workgroup is 8 waves = 256 agents on ONE hidden tile (its waves read the same 192 KB of weights through one L1); the 16
 //   tiles of an agent group are 16 workgroups dealt to the SAME XCD (workgroups go round-robin over the 8 XCDs), one after another: every
 //   L2 then holds the whole 3 MB of weights and fetches an agent group's x and h rows once for its 16 readers.
-//   State look-up as k_drqn_gru_f32: the LAST entry of the stably sorted previous ids equal to the agent's id, zeros if there is none;
-//   with an empty table the <false> variant skips the h half and takes gru_bias0.
-// k_drqn_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512 state units (h' rounded as the operand), float32 biases, then the
-//   dueling combination and torch.argmax's order (policy_f32_dev.h: q_epilogue, the f32 heads' own).
+//   The placement is policy_bf16_dev.h: xcd_place / xcd_grid, shared with the A2C's two GEMM kernels.
+//   State look-up as k_drqn_gru_f32 (policy_f32_dev.h: state_row): the LAST entry of the stably sorted previous ids equal to the agent's
+//   id, zeros if there is none; with an empty table the <false> variant skips the h half and takes gru_bias0.
+// k_drqn_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512 state units (policy_bf16_dev.h: head_gemm512_bf16, shared with
+//   k_a2c_head_bf16; h' rounded as the operand), float32 biases, then the dueling combination and torch.argmax's order
+//   (policy_f32_dev.h: q_epilogue, the f32 heads' own).
 //
 // Whole waves exit early; lanes past n repeat the last agent (their own columns of the MFMA, never stored).  NaN contract:
 // a NaN or Inf in an agent's inputs or state stays in that agent's MFMA column: it reaches its Q row and its new state and no other agent's.
@@ -44,21 +46,15 @@
 
 namespace {
 
-using magent_amd::f32::f32x16;
-using magent_amd::f32::f32x4;
-using magent_amd::f32::pingpong;
+using namespace magent_amd::bf16;         // the vector types, the conversions, xcd_place / xcd_grid, ring3, head_gemm512_bf16
 using magent_amd::f32::q_epilogue;
 using magent_amd::f32::out_of;
 using magent_amd::f32::sigmoid;
-
-using magent_amd::bf16::bf16x8;            // and the streamed-row blocks (policy_bf16_dev.h)
-using magent_amd::bf16::ring3;
-using magent_amd::bf16::round_bf16x8;
+using magent_amd::f32::state_row;
 
 constexpr int STATE = 512, GRU_TILES = STATE / 32, KSTEPS = STATE / 16;
 constexpr int GRU_WAVES = 8, GRU_THREADS = 64 * GRU_WAVES, GRU_CHUNK = 2;     // k-steps per register buffer; a wave has three buffers (ring3)
 constexpr int QH_WAVES = 4, QH_THREADS = 64 * QH_WAVES;
-constexpr int XCDS = 8;
 
 struct GruArgs {
     const bf16x8 *x;          // [n][64 units of 8]: the trunk's hidden layer, slot order
@@ -78,22 +74,12 @@ struct HOp { f32x4 a[2]; bf16x8 w[3]; };   // one k-step of the h half: eight fl
 template <bool HAS_H>
 __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_bf16(GruArgs A) {
     const int l = threadIdx.x & 63, w = threadIdx.x >> 6, g = l >> 5, r32 = l & 31;
-    // workgroup L runs on XCD L % 8; the j = L / 8 -th workgroup of an XCD is tile j % 16 of the XCD's (j / 16)-th agent group
-    const int j = blockIdx.x / XCDS, T = j % GRU_TILES, group = (j / GRU_TILES) * XCDS + blockIdx.x % XCDS;
+    int T, group;                                                // (policy_bf16_dev.h: the 16 tiles of an agent group on one XCD)
+    xcd_place(GRU_TILES, T, group);
     const int tile0 = (group * GRU_WAVES + w) * 32;
     if (group >= A.groups || tile0 >= A.n) return;               // (whole waves: the MFMAs below see every lane)
     const int agent = min(tile0 + r32, A.n - 1);
-    const float *hrow = nullptr;
-    if (HAS_H) {
-        const int id = A.ids[agent];
-        int lo = 0, hi = A.count;                                // lo: the first entry above id
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (A.prev_ids[mid] <= id) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo > 0 && A.prev_ids[lo - 1] == id) hrow = A.states + (size_t)A.rows[lo - 1] * STATE;
-    }
+    const float *hrow = HAS_H ? state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE) : nullptr;
     const bool have = hrow != nullptr;
     const bf16x8 *xp = A.x + (size_t)agent * (STATE / 8) + g;                 // k-step s: xp[2 s] = x[16 s + 8 g .. + 7]
     const f32x4 *hp = have ? (const f32x4 *)hrow + 2 * g : (const f32x4 *)xp; // k-step s: hp[4 s], hp[4 s + 1] = h[16 s + 8 g .. + 7]
@@ -184,23 +170,7 @@ __global__ void __launch_bounds__(QH_THREADS) k_drqn_head_bf16(QHeadArgs A) {
     if (tile0 >= A.n) return;
     const int agent = min(tile0 + r32, A.n - 1);
     const f32x4 *hp = (const f32x4 *)(A.h + (size_t)agent * STATE) + 2 * g;       // k-step s: hp[4 s], hp[4 s + 1]
-    f32x16 acc = {0};
-    // the operands of the next two k-steps load while the current two's MFMAs run
-    struct Op { f32x4 a[2]; bf16x8 w; };
-    Op op[2][2];
-    auto load = [&](int c, Op (&d)[2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int s = 2 * c + k;
-            d[k].a[0] = hp[4 * s]; d[k].a[1] = hp[4 * s + 1];
-            d[k].w = A.wh[s * 64 + l];
-        }
-    };
-    auto run = [&](const Op (&d)[2]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int k = 0; k < 2; k++) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d[k].w, round_bf16x8(d[k].a[0], d[k].a[1]), acc, 0, 0, 0);
-    };
-    pingpong<KSTEPS / 2>(op, load, run);
+    f32x16 acc = head_gemm512_bf16(A.wh, l, [&](int s) { return F8{{hp[4 * s], hp[4 * s + 1]}}; }, [](const F8 &v) { return round_bf16x8(v); });
 #pragma unroll
     for (int r = 0; r < 16; r++) acc[r] += A.bh[out_of(r, g)];
     // Q = acc + value - mean(advantage) (dueling) or acc, the argmax and the stores: q_epilogue
@@ -208,11 +178,7 @@ __global__ void __launch_bounds__(QH_THREADS) k_drqn_head_bf16(QHeadArgs A) {
                tile0 + r32 < A.n, agent, A.actions, A.q);
 }
 
-static size_t x_offset(const PolicyDqnShape *s, int n) {       // the trunk's workspace, then x
-    size_t act = 0;
-    policy_dqn_act_bytes(s, n, &act);
-    return (act + 255) / 256 * 256;
-}
+static size_t x_offset(const PolicyDqnShape *s, int n) { return magent_amd::drqn_x_offset(policy_dqn_act_bytes, s, n); }      // policy_host.h
 
 static int drqn_infer(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const void *view_any, bool cells16, const float *feat, int n,
                       const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
@@ -232,7 +198,7 @@ static int drqn_infer(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const
     G.x = (const bf16x8 *)x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.count = count; G.n = n;
     G.groups = (n + 32 * GRU_WAVES - 1) / (32 * GRU_WAVES);
     G.w = (const bf16x8 *)w->gru; G.bias = count > 0 ? w->gru_bias : w->gru_bias0; G.out = new_states;
-    const dim3 ggrid((unsigned)((G.groups + XCDS - 1) / XCDS * XCDS * GRU_TILES));
+    const dim3 ggrid(xcd_grid(G.groups, GRU_TILES));
     if (count > 0) hipLaunchKernelGGL(k_drqn_gru_bf16<true>, ggrid, dim3(GRU_THREADS), 0, st, G);
     else hipLaunchKernelGGL(k_drqn_gru_bf16<false>, ggrid, dim3(GRU_THREADS), 0, st, G);
     QHeadArgs Q{};

@@ -21,7 +21,7 @@
 //   the x rows of an agent group are read by the 16 hidden tiles' workgroups (L2).  The gates are applied in registers and h' goes
 //   straight to the new state table.
 //   The previous state of an agent is the row of the previous call whose id is the LAST equal entry of that call's ids sorted stably
-//   (binary search: duplicates -- the dict's last occurrence); an id not found starts from zeros.  With an empty table the <false>
+//   (policy_f32_dev.h: state_row, the bf16 kernel's too -- binary search: duplicates, the dict's last occurrence); an id not found starts from zeros.  With an empty table the <false>
 //   variant skips the h half and takes the biases of a zero state (W_h 0 + b_h, which the host computes: NaN where W_h holds a
 //   non-finite weight, as torch's W_h @ 0).
 // k_drqn_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 state units (policy_f32_dev.h: head_gemm512, shared with
@@ -65,17 +65,7 @@ __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_f32(GruArgs A) {
     if (tile0 >= A.n) return;                                    // (whole waves: the MFMAs below see every lane)
     const int T = blockIdx.y;
     const int agent = min(tile0 + r32, A.n - 1);
-    const float *hrow = nullptr;
-    if (HAS_H) {
-        const int id = A.ids[agent];
-        int lo = 0, hi = A.count;                                // lo: the first entry above id
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (A.prev_ids[mid] <= id) lo = mid + 1;
-            else hi = mid;
-        }
-        if (lo > 0 && A.prev_ids[lo - 1] == id) hrow = A.states + (size_t)A.rows[lo - 1] * STATE;
-    }
+    const float *hrow = HAS_H ? state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE) : nullptr;
     const bool have = hrow != nullptr;
     const f32x4 *xp = (const f32x4 *)(A.x + (size_t)agent * STATE) + g;       // group m: xp[2 m] = x[8 m + 4 g .. + 3]
     const f32x4 *hp = have ? (const f32x4 *)hrow + g : xp;                    // (a lane without a state reads x and takes zeros)
@@ -154,11 +144,7 @@ __global__ void __launch_bounds__(QH_THREADS) k_drqn_head_f32(QHeadArgs A) {
                tile0 + r32 < A.n, agent, A.actions, A.q);
 }
 
-static size_t x_offset(const PolicyDqnShape *s, int n) {       // the trunk's workspace, then x
-    size_t act = 0;
-    policy_dqn_f32_act_bytes(s, n, &act);
-    return (act + 255) / 256 * 256;
-}
+static size_t x_offset(const PolicyDqnShape *s, int n) { return magent_amd::drqn_x_offset(policy_dqn_f32_act_bytes, s, n); }      // policy_host.h
 
 }  // namespace
 

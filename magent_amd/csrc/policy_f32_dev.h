@@ -10,14 +10,18 @@
 //   head_gemm512                                     the one-wave K = 512, 32-output head GEMM (k_drqn_head_f32, k_a2c_head_f32)
 //   q_epilogue                                       the dueling combination, torch.argmax's pick, the stores (k_dqn_head_f32, k_drqn_head_f32)
 //   policy_epilogue                                  softmax, clamp, the stores and the inverse-CDF draw (k_a2c_head_f32, k_a2c_head_bf16)
-//   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, k_drqn_gru_bf16)
-// policy_drqn_bf16.hip takes out_of, sigmoid, q_epilogue and pingpong from here too (its gates, blend and epilogue are float32), and
-// policy_a2c_bf16.hip out_of, relu and policy_epilogue.
+//   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, head_gemm512_bf16)
+//   state_row                                        the id table's look-up (k_drqn_gru_f32, k_drqn_gru_bf16)
+//   colsum_part, colsum_blocks                       the CommNet column sums' bodies (the four k_a2c_colsum* kernels)
+// The bf16 files take their float32 side from here too (policy_bf16_dev.h includes this header): policy.hip the vector types, out_of
+// and q_before; policy_drqn_bf16.hip out_of, sigmoid, q_epilogue and state_row (its gates, blend and epilogue are float32);
+// policy_a2c_bf16.hip out_of, relu, policy_epilogue and the column sums.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "../../include/magent_policy.h"
+#include "policy_host.h"
 
 namespace magent_amd {
 namespace f32 {
@@ -273,6 +277,38 @@ __device__ __forceinline__ void pingpong(Buf (&op)[2], const Load &load, const R
         if (c + 2 < NC) load(c + 2, op[0]);
         run(op[1]);
     }
+}
+
+// ---------------------------------------------------------------------------------------------------- the DRQN's id table
+// The state row (`pitch` floats) of agent `id`: the row of the LAST entry equal to id of the previous call's ids sorted stably (binary
+// search; duplicates -- the dict's last occurrence), or null if there is none (the agent starts from zeros).
+__device__ __forceinline__ const float *state_row(int id, const int *prev_ids, const int *rows, int count, const float *states, int pitch) {
+    int lo = 0, hi = count;                                      // lo: the first entry above id
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (prev_ids[mid] <= id) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && prev_ids[lo - 1] == id ? states + (size_t)rows[lo - 1] * pitch : nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------- column sums in a fixed order
+// Workgroups of A2C_HID threads, thread c = column c.  colsum_part: block b adds agents A2C_CS_BLOCK b .. + A2C_CS_BLOCK - 1 of the
+// call in agent order, at(i) = element i of the rows [n][A2C_HID] as float32; colsum_blocks: one workgroup adds the blocks in block order.
+template <class At>
+__device__ __forceinline__ void colsum_part(int n, float *part, const At &at) {
+    const int c = threadIdx.x, beg = blockIdx.x * A2C_CS_BLOCK, end = min(beg + A2C_CS_BLOCK, n);
+    float s = 0.0f;
+#pragma unroll 16
+    for (int a = beg; a < end; a++) s += at((size_t)a * A2C_HID + c);
+    part[(size_t)blockIdx.x * A2C_HID + c] = s;
+}
+__device__ __forceinline__ void colsum_blocks(const float *part, int n_blocks, float *sum) {
+    const int c = threadIdx.x;
+    float s = 0.0f;
+#pragma unroll 32
+    for (int b = 0; b < n_blocks; b++) s += part[(size_t)b * A2C_HID + c];
+    sum[c] = s;
 }
 
 // The DQN's trunk for the DRQN: k_dqn_conv_f32, then k_dqn_head_f32 stopped after its hidden layer, which it stores as

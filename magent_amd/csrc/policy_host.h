@@ -1,8 +1,13 @@
-// policy_host.h -- the host side every policy launcher starts with (policy.hip and the three policy_*_f32.hip; internal, not part of the C-ABI).
+// policy_host.h -- the host side of the policy launchers (policy.hip, policy_f32.hip and the four policy_drqn_* / policy_a2c_* files;
+// internal, not part of the C-ABI): StreamDevice and LdsAllowance, which every launcher starts with, the DRQN's and the A2C's workspace
+// layouts, each taking what differs between float32 and bf16 (the trunk's act-bytes function; the size of a row element).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 
 #include <initializer_list>
+
+#include "../../include/magent_policy.h"
 
 namespace magent_amd {
 
@@ -37,5 +42,29 @@ struct LdsAllowance {
         return done[dev] = true;
     }
 };
+
+// The DRQN's workspace: the trunk's own (act_bytes: policy_dqn_act_bytes or policy_dqn_f32_act_bytes), then x from the next 256 bytes on
+inline size_t drqn_x_offset(int (*act_bytes)(const PolicyDqnShape *, int, size_t *), const PolicyDqnShape *s, int n) {
+    size_t act = 0;
+    act_bytes(s, n, &act);
+    return (act + 255) / 256 * 256;
+}
+
+// The A2C's workspace, rows of A2C_HID elements of `elem` bytes: x and h0; with CommNet h1, the column sums' partial sums (float32, one
+// row per block of A2C_CS_BLOCK agents) and the sums.  Every part starts on a multiple of 256 bytes.
+constexpr int A2C_HID = 512, A2C_CS_BLOCK = 256;
+struct A2cLayout { size_t x, h0, h1, part, sum, bytes; int n_blocks; };
+inline A2cLayout a2c_layout(int n, bool comm, size_t elem) {
+    auto up256 = [](size_t v) { return (v + 255) / 256 * 256; };
+    A2cLayout L{};
+    const size_t rows = up256((size_t)n * A2C_HID * elem);
+    L.n_blocks = (n + A2C_CS_BLOCK - 1) / A2C_CS_BLOCK;
+    L.x = 0; L.h0 = rows; L.bytes = 2 * rows;
+    if (comm) {
+        L.h1 = L.bytes; L.part = L.h1 + rows; L.sum = L.part + up256((size_t)L.n_blocks * A2C_HID * sizeof(float));
+        L.bytes = L.sum + A2C_HID * sizeof(float);
+    }
+    return L;
+}
 
 }  // namespace magent_amd

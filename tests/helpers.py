@@ -71,6 +71,23 @@ def build_policy_emu(name, sources, headers, caller):
     return lib
 
 
+# The emulated library of every policy source set: name -> (sources, headers copied beside them).  One list per set, here and nowhere
+# else: a block that moves to another header cannot leave a stale list behind in a test file.  "policy": all six, for tools/policy_bits.py.
+_POLICY_HEADERS = ["policy_bf16_dev.h", "policy_f32_dev.h", "policy_host.h", "tune.h"]
+POLICY_EMU = {
+    "drqn": (["policy_f32.hip", "policy_drqn_f32.hip"], _POLICY_HEADERS[1:]),
+    "a2c": (["policy_a2c_f32.hip"], _POLICY_HEADERS[1:3]),
+    "drqn_bf16": (["policy.hip", "policy_drqn_bf16.hip"], _POLICY_HEADERS),
+    "a2c_bf16": (["policy_a2c_bf16.hip"], _POLICY_HEADERS[:3]),
+    "policy": (["policy.hip", "policy_f32.hip", "policy_drqn_f32.hip", "policy_drqn_bf16.hip", "policy_a2c_f32.hip", "policy_a2c_bf16.hip"], _POLICY_HEADERS),
+}
+
+
+def policy_emu(name):
+    """the emulated library of the policy source set `name` (POLICY_EMU), built by build_policy_emu"""
+    return build_policy_emu(name, POLICY_EMU[name][0], POLICY_EMU[name][1], __file__)
+
+
 class PolicyLeg(object):
     """one of the two legs of a policy-kernel test.  `emu`: an emulated build (`emu_lib()` returns its path) on CPU tensors, with
     MAGENT_TUNE=`tune` if given (read at the library's first call); `gpu`: the product library on cuda:0.
@@ -121,6 +138,69 @@ def make_policy_inputs(view_space, feat, n, seed, extra=0, fill=0.0):
     view[n:] = fill
     featv[n:] = fill
     return view, featv
+
+
+def make_rnet(vs, feat, A, dueling, seed, dev="cpu", scale=3.0):
+    import torch
+    from magent_amd.builtin.torch_model.drqn import _RecurrentQNet
+    torch.manual_seed(seed)
+    q = _RecurrentQNet(vs, (feat,), A, dueling)
+    with torch.no_grad():
+        for p in q.parameters():          # larger weights than the default init: every layer matters in Q and in the gates
+            p.mul_(scale)
+    return q.to(dev)
+
+
+class DictModel(object):
+    """the Python-dict path's state semantics (drqn.py: agent_states), over the kernels' own output rows (S units each)"""
+
+    def __init__(self, S=512):
+        self.states, self.S = {}, S
+
+    def lookup(self, ids):
+        zero = np.zeros(self.S, np.float32)
+        return np.stack([self.states.get(int(i), zero) for i in ids]) if len(ids) else np.zeros((0, self.S), np.float32)
+
+    def store(self, ids, h):
+        self.states = {int(i): h[k] for k, i in enumerate(ids)}
+
+
+def cells_of(view):
+    """the engine's bf16 cells of a float32 view (a torch tensor; on its device), as env_get_observation_device_bf16 defines them: the
+    channels rounded to nearest even, zeros, 1.0 in channel 7"""
+    import torch
+    n, h, w, c = view.shape
+    cells = torch.zeros((n, h, w, 8), dtype=torch.bfloat16, device=view.device)
+    cells[..., :c] = view.to(torch.bfloat16)
+    cells[..., 7] = 1.0
+    return cells
+
+
+class SpacesEnv(object):          # a model's constructor reads the spaces only
+    device_id = 0
+
+    def __init__(self, vs=(9, 9, 5), feat=20, A=13):
+        self.vs, self.feat, self.A = vs, feat, A
+
+    def get_view_space(self, h):
+        return self.vs
+
+    def get_feature_space(self, h):
+        return (self.feat,)
+
+    def get_action_space(self, h):
+        return (self.A,)
+
+
+def battle(seed, device_obs=True, n=300, size=40):
+    """a battle of n random agents a side on the product engine with device-resident observations (True: float32 views, "bf16": cells)"""
+    env = magent_amd.GridWorld("battle", map_size=size, device_obs=device_obs)
+    env.set_seed(seed)
+    env.reset()
+    hs = env.get_handles()
+    for h in hs:
+        env.add_agents(h, "random", n=n)
+    return env, hs
 
 
 def net_params(net):

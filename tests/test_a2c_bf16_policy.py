@@ -28,29 +28,10 @@ import test_a2c_policy as F32
 
 NAN, INF = float("nan"), float("inf")
 HID = 512
-HEADERS = ["policy_bf16_dev.h", "policy_f32_dev.h", "policy_host.h"]
-
-
-def build_emu():
-    """policy_a2c_bf16.hip as a library of its own (helpers.build_policy_emu)"""
-    return H.build_policy_emu("a2c_bf16", ["policy_a2c_bf16.hip"], HEADERS, __file__)
-
-
-leg, LEGS = H.policy_legs(build_emu, policy_class="HipA2cPolicy")
-make_inputs, make_net, np_draw = H.make_policy_inputs, F32.make_net, F32.np_draw
+leg, LEGS = H.policy_legs(lambda: H.policy_emu("a2c_bf16"), policy_class="HipA2cPolicy")
+make_inputs, make_net, np_draw, cells_of, _Env, _battle = H.make_policy_inputs, F32.make_net, F32.np_draw, H.cells_of, H.SpacesEnv, H.battle
 COMM = [pytest.param(False, id="plain"), pytest.param(True, id="comm")]
 CELLS = [pytest.param(False, id="f32views"), pytest.param(True, id="bf16cells")]
-
-
-def cells_of(view):
-    """the engine's bf16 cells of a float32 view, as env_get_observation_device_bf16 defines them: the channels rounded to nearest even,
-    zeros, 1.0 in channel 7"""
-    import torch
-    n, h, w, c = view.shape
-    cells = torch.zeros((n, h, w, 8), dtype=torch.bfloat16)
-    cells[..., :c] = view.to(torch.bfloat16)
-    cells[..., 7] = 1.0
-    return cells
 
 
 def has_cells(vs):
@@ -451,22 +432,6 @@ def test_reordering_spread():
 
 
 # ---------------------------------------------------------------------------------------------------- 7. the public class, CPU only
-class _Env(object):          # the model's constructor reads the spaces only
-    device_id = 0
-
-    def __init__(self, vs=(9, 9, 5), feat=20, A=13):
-        self.vs, self.feat, self.A = vs, feat, A
-
-    def get_view_space(self, h):
-        return self.vs
-
-    def get_feature_space(self, h):
-        return (self.feat,)
-
-    def get_action_space(self, h):
-        return (self.A,)
-
-
 def test_public_class_takes_infer_dtype_on_the_cpu(monkeypatch):
     import torch
     from magent_amd.builtin.torch_model import AdvantageActorCritic
@@ -500,17 +465,6 @@ def test_public_class_takes_infer_dtype_on_the_cpu(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------- 8. the public class on the GPU
-def _battle(seed, device_obs, n=300, size=40):
-    import magent_amd
-    env = magent_amd.GridWorld("battle", map_size=size, device_obs=device_obs)
-    env.set_seed(seed)
-    env.reset()
-    hs = env.get_handles()
-    for h in hs:
-        env.add_agents(h, "random", n=n)
-    return env, hs
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("comm", COMM)
 @pytest.mark.parametrize("device_obs", ["bf16", True], ids=["bf16cells", "f32views"])

@@ -28,13 +28,8 @@ TORCH_P_ERR, TORCH_V_ERR, ORDER_FACTOR = 6.3e-7, 5.9e-7, 4.0
 P_WORK, V_WORK = ORDER_FACTOR * TORCH_P_ERR, ORDER_FACTOR * TORCH_V_ERR
 
 
-def build_a2c_emu():
-    """policy_a2c_f32.hip as a library of its own (helpers.build_policy_emu)"""
-    return H.build_policy_emu("a2c", ["policy_a2c_f32.hip"], ["policy_f32_dev.h", "policy_host.h"], __file__)
-
-
-leg, LEGS = H.policy_legs(build_a2c_emu, policy_class="HipA2cPolicyF32")      # the two legs
-make_inputs, net_params = H.make_policy_inputs, H.net_params
+leg, LEGS = H.policy_legs(lambda: H.policy_emu("a2c"), policy_class="HipA2cPolicyF32")      # the two legs
+make_inputs, net_params, _battle = H.make_policy_inputs, H.net_params, H.battle
 COMM = [pytest.param(False, id="plain"), pytest.param(True, id="comm")]
 
 
@@ -410,17 +405,6 @@ def test_a2c_writes_nothing_outside_its_buffers(lg, comm):
 
 
 # ---------------------------------------------------------------------------------------------------- 6. the model on the GPU
-def _battle(seed, n=300, size=40):
-    import magent_amd
-    env = magent_amd.GridWorld("battle", map_size=size, device_obs=True)
-    env.set_seed(seed)
-    env.reset()
-    hs = env.get_handles()
-    for h in hs:
-        env.add_agents(h, "random", n=n)
-    return env, hs
-
-
 class _Env(object):
     def __init__(self, key, value):
         self.key, self.value = key, value

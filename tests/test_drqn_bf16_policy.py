@@ -28,38 +28,8 @@ import helpers as H
 
 NAN, INF = float("nan"), float("inf")
 S = 512
-HEADERS = ["policy_bf16_dev.h", "policy_f32_dev.h", "policy_host.h", "tune.h"]
-
-
-def build_emu():
-    """policy.hip + policy_drqn_bf16.hip as a library of their own (helpers.build_policy_emu)"""
-    return H.build_policy_emu("drqn_bf16", ["policy.hip", "policy_drqn_bf16.hip"], HEADERS, __file__)
-
-
-leg, LEGS = H.policy_legs(build_emu, policy_class="HipDrqnPolicy")
-make_inputs = H.make_policy_inputs
-
-
-def make_rnet(vs, feat, A, dueling, seed, dev="cpu", scale=3.0):
-    import torch
-    from magent_amd.builtin.torch_model.drqn import _RecurrentQNet
-    torch.manual_seed(seed)
-    q = _RecurrentQNet(vs, (feat,), A, dueling)
-    with torch.no_grad():
-        for p in q.parameters():          # larger weights than the default init: every layer matters in Q and in the gates
-            p.mul_(scale)
-    return q.to(dev)
-
-
-def cells_of(view):
-    """the engine's bf16 cells of a float32 view, as env_get_observation_device_bf16 defines them: the channels rounded to nearest even,
-    zeros, 1.0 in channel 7"""
-    import torch
-    n, h, w, c = view.shape
-    cells = torch.zeros((n, h, w, 8), dtype=torch.bfloat16)
-    cells[..., :c] = view.to(torch.bfloat16)
-    cells[..., 7] = 1.0
-    return cells
+leg, LEGS = H.policy_legs(lambda: H.policy_emu("drqn_bf16"), policy_class="HipDrqnPolicy")
+make_inputs, make_rnet, DictModel, cells_of, _Env, _battle = H.make_policy_inputs, H.make_rnet, H.DictModel, H.cells_of, H.SpacesEnv, H.battle
 
 
 # ---------------------------------------------------------------------------------------------------- the rounding reference
@@ -102,19 +72,6 @@ def bounds(q_ref, h_ref):
     qm = float(np.abs(fin(q_ref)).max()) if np.isfinite(q_ref).any() else 0.0
     hm = float(np.abs(fin(h_ref)).max()) if np.isfinite(h_ref).any() else 0.0
     return 4 * SPREAD_Q * (2e-3 * qm + 2e-3), 4 * SPREAD_H * (2e-3 * max(1.0, hm) + 2e-3)
-
-
-class DictModel(object):
-    """the Python-dict path's state semantics (drqn.py: agent_states), over the kernels' own output rows"""
-
-    def __init__(self):
-        self.states = {}
-
-    def lookup(self, ids):
-        return np.stack([self.states.get(int(i), np.zeros(S, np.float32)) for i in ids]) if len(ids) else np.zeros((0, S), np.float32)
-
-    def store(self, ids, h):
-        self.states = {int(i): h[k] for k, i in enumerate(ids)}
 
 
 def check_against_ref(tag, net, view, featv, h_prev, actions, q, h2, A, want_clear=False):
@@ -290,8 +247,7 @@ def test_drqn_states_move_between_the_f32_and_the_bf16_path(lg):
     lg = leg(lg)
     lib32 = None
     if lg.name == "emu":
-        lib32 = ctypes.CDLL(H.build_policy_emu("drqn", ["policy_f32.hip", "policy_drqn_f32.hip"], ["policy_f32_dev.h", "policy_host.h", "tune.h"],
-                                               os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_drqn_policy.py")), mode=os.RTLD_LOCAL)
+        lib32 = ctypes.CDLL(H.policy_emu("drqn"), mode=os.RTLD_LOCAL)
         from magent_amd import c_lib
         c_lib.declare_policy(lib32)
     vs, feat, A = (9, 9, 3), 12, 9
@@ -535,22 +491,6 @@ def test_reordering_spread_and_clear_agents():
 
 
 # ---------------------------------------------------------------------------------------------------- 7. the public class, CPU only
-class _Env(object):          # the model's constructor reads the spaces only
-    device_id = 0
-
-    def __init__(self, vs=(9, 9, 5), feat=20, A=13):
-        self.vs, self.feat, self.A = vs, feat, A
-
-    def get_view_space(self, h):
-        return self.vs
-
-    def get_feature_space(self, h):
-        return (self.feat,)
-
-    def get_action_space(self, h):
-        return (self.A,)
-
-
 def test_public_class_takes_infer_dtype_on_the_cpu(monkeypatch):
     import torch
     from magent_amd.builtin.torch_model import DeepRecurrentQNetwork
@@ -585,17 +525,6 @@ def test_public_class_takes_infer_dtype_on_the_cpu(monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------- 8. / 9. the public class on the GPU
-def _battle(seed, device_obs, n=300, size=40):
-    import magent_amd
-    env = magent_amd.GridWorld("battle", map_size=size, device_obs=device_obs)
-    env.set_seed(seed)
-    env.reset()
-    hs = env.get_handles()
-    for h in hs:
-        env.add_agents(h, "random", n=n)
-    return env, hs
-
-
 def _torch_model(env, h, name, **kw):
     from magent_amd.builtin.torch_model import DeepRecurrentQNetwork
     old = os.environ.get("MAGENT_POLICY_F32")

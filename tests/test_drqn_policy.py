@@ -20,25 +20,9 @@ NAN, INF = float("nan"), float("inf")
 S = 512
 
 
-def build_drqn_emu():
-    """policy_f32.hip + policy_drqn_f32.hip as a library of their own (helpers.build_policy_emu)"""
-    return H.build_policy_emu("drqn", ["policy_f32.hip", "policy_drqn_f32.hip"], ["policy_f32_dev.h", "policy_host.h", "tune.h"], __file__)
-
-
 # the two legs; on the emulator three conv workgroups walk every tile
-leg, LEGS = H.policy_legs(build_drqn_emu, tune="policy_grid=3", policy_class="HipDrqnPolicyF32")
-make_inputs, net_params = H.make_policy_inputs, H.net_params
-
-
-def make_rnet(vs, feat, A, dueling, seed, dev="cpu", scale=3.0):
-    import torch
-    from magent_amd.builtin.torch_model.drqn import _RecurrentQNet
-    torch.manual_seed(seed)
-    q = _RecurrentQNet(vs, (feat,), A, dueling)
-    with torch.no_grad():
-        for p in q.parameters():          # larger weights than the default init: every layer matters in Q and in the gates
-            p.mul_(scale)
-    return q.to(dev)
+leg, LEGS = H.policy_legs(lambda: H.policy_emu("drqn"), tune="policy_grid=3", policy_class="HipDrqnPolicyF32")
+make_inputs, net_params, make_rnet, DictModel, _battle = H.make_policy_inputs, H.net_params, H.make_rnet, H.DictModel, H.battle
 
 
 # ---------------------------------------------------------------------------------------------------- float64
@@ -112,19 +96,6 @@ def error_bounds(P, view, feature, h, h64, vs, feat, A, dueling):
 
 
 # ---------------------------------------------------------------------------------------------------- one checked call
-class DictModel(object):
-    """the Python-dict path's state semantics (drqn.py: agent_states), over the kernels' own output rows"""
-
-    def __init__(self):
-        self.states = {}
-
-    def lookup(self, ids):
-        return np.stack([self.states.get(int(i), np.zeros(S, np.float32)) for i in ids]) if len(ids) else np.zeros((0, S), np.float32)
-
-    def store(self, ids, h):
-        self.states = {int(i): h[k] for k, i in enumerate(ids)}
-
-
 WORST = {}
 
 
@@ -338,17 +309,6 @@ def test_drqn_supported_is_the_dqn_region():
 
 
 # ---------------------------------------------------------------------------------------------------- 5. the model on the GPU
-def _battle(seed, n=300, size=40):
-    import magent_amd
-    env = magent_amd.GridWorld("battle", map_size=size, device_obs=True)
-    env.set_seed(seed)
-    env.reset()
-    hs = env.get_handles()
-    for h in hs:
-        env.add_agents(h, "random", n=n)
-    return env, hs
-
-
 def _models(env, h, use_dueling=True):
     """the same network twice: the kernel path and, with MAGENT_POLICY_F32=torch, the PyTorch path"""
     import torch

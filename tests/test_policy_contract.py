@@ -24,7 +24,7 @@ NAN, INF = float("nan"), float("inf")
 # ---------------------------------------------------------------------------------------------------- the two legs
 # `emu`: the engine-wide emulated build on CPU tensors (three workgroups walk every tile); `gpu`: the product library on cuda:0
 leg, LEGS = H.policy_legs(H.ensure_emu, tune="policy_grid=3")
-make_inputs = H.make_policy_inputs
+make_inputs, cells_of = H.make_policy_inputs, H.cells_of
 
 
 def make_qnet(view_space, feat, n_action, seed, dev="cpu", scale=3.0):
@@ -45,15 +45,6 @@ def policy(lg, kind, qnet, view_space, feat, n_action):
     pol.pack()
     assert all(t.device.type == lg.dev.type for t in pol._packed.values())       # (the kernels dereference these addresses)
     return pol
-
-
-def cells_of(view):
-    """the engine's bf16 cells of float32 views: channels, zeros, 1.0 in channel 7"""
-    import torch
-    c = torch.zeros(view.shape[:3] + (8,), dtype=torch.bfloat16, device=view.device)
-    c[..., :view.shape[3]] = view.to(torch.bfloat16)
-    c[..., 7] = 1.0
-    return c.contiguous()
 
 
 def act_bytes(lg, kind, pol, n):
