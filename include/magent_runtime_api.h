@@ -141,7 +141,9 @@ int env_step_many(EnvHandle *games, int n, int *done);
  *   - every other world runs the calls one after the other on n_threads host threads inside the library.
  * `actions` must hold the actions BEFORE the call (they are read by the second launch, in
  * stream order after the render -- the caller's policy reads the observation of the PREVIOUS cycle, or orders its own
- * stream with env_get_stream); the outputs are complete when the call returns (the host has waited for `done`). */
+ * stream with env_get_stream); the outputs are complete when the call returns (the host has waited for `done`).
+ * Concurrent calls from several host threads over disjoint sets of environments are supported (the library's worker threads serve one
+ * call's round at a time). */
 int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float **feat, const int **actions,
                    float **rewards, int *done, int n_threads);
 /* env_cycle_many with the view format chosen PER ENTRY: view_cells[e * n_group + g] != 0 says that view[e * n_group + g] is a bf16-cell
@@ -155,6 +157,11 @@ int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float
  * 7 channels, or one that is not 16-byte aligned, is FATAL as in env_get_observation_device_bf16. */
 int env_cycle_many_cells(EnvHandle *games, int n_env, int n_group, void **view, const unsigned char *view_cells,
                          float **feat, const int **actions, float **rewards, int *done, int n_threads);
+/* What the library's host-thread pool -- the workers of env_cycle_many(_cells) that run the environments of the third form -- has done in
+ * this process so far: out[0] rounds (calls that handed two or more environments to it with n_threads >= 2), out[1] environment cycles
+ * ("items") run in them, out[2] those of them run by worker threads and not by the calling thread, out[3] the most distinct threads that
+ * ran at least one item in one round.  Relaxed counters, read-only, for tests and tuning; no device work. */
+int env_cycle_pool_stats(long long out[4]);
 /* out[e * n_group + g] = number of agents of group g in environment e (env_get_info "num" for a whole batch; host only) */
 int env_num_many(EnvHandle *games, int n_env, int n_group, int *out);
 /* wait until everything enqueued on the environment's stream has finished */

@@ -47,6 +47,7 @@ DEVICE_ABI = [
     ("env_step_many", [_c.POINTER(_vp), _i, _ip]),
     ("env_cycle_many", [_c.POINTER(_vp), _i, _i, _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _ip, _i]),
     ("env_cycle_many_cells", [_c.POINTER(_vp), _i, _i, _c.POINTER(_vp), _c.POINTER(_c.c_ubyte), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _ip, _i]),
+    ("env_cycle_pool_stats", [_c.POINTER(_c.c_longlong)]),
     ("env_num_many", [_c.POINTER(_vp), _i, _i, _ip]),
     ("env_sync", [_vp]),
     ("env_get_stream", [_vp, _c.POINTER(_vp)]),

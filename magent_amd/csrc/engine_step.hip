@@ -23,9 +23,8 @@ void Env::set_action_device(int g, const int *d_act) {
         int h_flag = 0;
         read_back(&h_flag, flag, sizeof(int));
         goals_act = h_flag != 0;
-        static bool told = false;
-        if (goals_act && !told) {
-            told = true;
+        static std::atomic<bool> told{false};      // (set_action_device runs on env_cycle_many's worker threads too)
+        if (goals_act && !told.exchange(true, std::memory_order_relaxed)) {
             std::fprintf(stderr, "magent-amd: a group of goals (can_absorb) was given actions that move, turn or attack: such steps run the reference's "
                                  "sequential loops on one lane of the device -- exact, about a microsecond per action of the whole world (INTEGRATION.md)\n");
         }

@@ -1,15 +1,12 @@
 // runtime_api.hip -- the C-ABI of libmagent.so (include/magent_runtime_api.h): thin trampolines onto Env.
 // Replaces reference src/runtime_api.cc:15-163 symbol for symbol; PART 2 adds the device-resident calls.
-#include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/magent_runtime_api.h"
+#include "cycle_pool.h"
 #include "engine_host.h"
 
 using magent_amd::Env;
@@ -20,54 +17,8 @@ static inline Env *E(EnvHandle h) {
     return (Env *)h;
 }
 
-// Worker threads of env_cycle_many: started once, parked on a condition variable between rounds (creating threads
-// per call cost more than a small world's whole step).  One round at a time (rounds are serialised by `round_mutex`).
 namespace {
-class CyclePool {
-public:
-    void run(int n_threads, int n_items, const std::function<void(int)> &fn) {
-        std::lock_guard<std::mutex> round(round_mutex);
-        {
-            std::unique_lock<std::mutex> lk(m);
-            while ((int)workers.size() < n_threads - 1) workers.emplace_back([this] { loop(); });
-            job = &fn; total = n_items; next = 0; pending = std::min(n_threads - 1, (int)workers.size()); active = pending; epoch++;
-        }
-        cv.notify_all();
-        for (int e; (e = next.fetch_add(1)) < n_items;) fn(e);     // the calling thread works too
-        std::unique_lock<std::mutex> lk(m);
-        done_cv.wait(lk, [this] { return pending == 0; });
-        job = nullptr;
-    }
-    ~CyclePool() {
-        { std::unique_lock<std::mutex> lk(m); quit = true; }
-        cv.notify_all();
-        for (auto &t : workers) t.join();
-    }
-private:
-    void loop() {
-        unsigned seen = 0;
-        std::unique_lock<std::mutex> lk(m);
-        while (true) {
-            cv.wait(lk, [&] { return quit || (epoch != seen && active > 0); });
-            if (quit) return;
-            seen = epoch; active--;
-            const std::function<void(int)> *fn = job;
-            const int n = total;
-            lk.unlock();
-            for (int e; (e = next.fetch_add(1)) < n;) (*fn)(e);
-            lk.lock();
-            if (--pending == 0) done_cv.notify_one();
-        }
-    }
-    std::mutex m, round_mutex;
-    std::condition_variable cv, done_cv;
-    std::vector<std::thread> workers;
-    const std::function<void(int)> *job = nullptr;
-    std::atomic<int> next{0};
-    int total = 0, pending = 0, active = 0;
-    unsigned epoch = 0;
-    bool quit = false;
-};
+using magent_amd::CyclePool;     // (cycle_pool.h: no HIP in it, so that a stand-alone program can run it under ThreadSanitizer)
 CyclePool &cycle_pool() { static CyclePool *p = new CyclePool(); return *p; }   // never destroyed: no join at process exit
 }  // namespace
 
@@ -158,6 +109,8 @@ int env_cycle_many(EnvHandle *games, int n_env, int n_group, float **view, float
                    float **rewards, int *done, int n_threads) {
     return env_cycle_many_cells(games, n_env, n_group, (void **)view, nullptr, feat, actions, rewards, done, n_threads);
 }
+// what the host-thread pool of env_cycle_many has done in this process so far (relaxed counters; read-only)
+int env_cycle_pool_stats(long long out[4]) { cycle_pool().stats(out); return 0; }
 // agent counts of n_env environments x n_group groups in one call (the host mirror: no device work)
 int env_num_many(EnvHandle *games, int n_env, int n_group, int *out) {
     for (int e = 0; e < n_env; e++) {

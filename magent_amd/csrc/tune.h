@@ -51,29 +51,34 @@ inline void tune_refuse_removed_variables() {
         }
 }
 
-inline int tune(const char *key, int dflt) {
-    static const bool legacy_checked = (tune_refuse_removed_variables(), true);
-    (void)legacy_checked;
+// every entry of MAGENT_TUNE names a known key, or the process ends.  Called once per process (tune's static initialiser)
+inline bool tune_check_entries(const char *s) {
     static const char *const known[] = {"checked_step", "host_shuffle", "attack_pairs", "move_batches", "solo_step", "solo_max", "batch_solo_max", "scan_solo_max", "overlap",
                                         "fold_minimap", "render", "render_sweep", "render_su", "render_depth", "att_threads", "policy_grid", "policy_stamps",
                                         "batch_cycle", "early_report", "touch_map", "batch_pipe", "batch_pipe_min", "pipe_sweep", "pipe_span", "pipe_own"};
+    for (const char *p = s; *p;) {
+        const char *e = std::strchr(p, ',');
+        const size_t len = e ? (size_t)(e - p) : std::strlen(p);
+        const char *eq = (const char *)std::memchr(p, '=', len);
+        bool ok = false;
+        if (eq)
+            for (const char *k : known) ok |= std::strlen(k) == (size_t)(eq - p) && !std::strncmp(k, p, (size_t)(eq - p));
+        if (!ok && len) { std::fprintf(stderr, "magent-amd FATAL: MAGENT_TUNE: unknown entry \"%.*s\" (see magent_amd/csrc/tune.h)\n", (int)len, p); std::abort(); }
+        if (!e) break;
+        p = e + 1;
+    }
+    return true;
+}
+
+// (callable from several threads at once -- env_cycle_many's workers reach it from different `static const` sites, whose guards are
+// different: the one-time checks are function-local static initialisers, which C++11 runs once and under a lock)
+inline int tune(const char *key, int dflt) {
+    static const bool legacy_checked = (tune_refuse_removed_variables(), true);
+    (void)legacy_checked;
     const char *s = std::getenv("MAGENT_TUNE");
     if (!s || !*s) return dflt;
-    static bool checked = false;
-    if (!checked) {
-        checked = true;
-        for (const char *p = s; *p;) {
-            const char *e = std::strchr(p, ',');
-            const size_t len = e ? (size_t)(e - p) : std::strlen(p);
-            const char *eq = (const char *)std::memchr(p, '=', len);
-            bool ok = false;
-            if (eq)
-                for (const char *k : known) ok |= std::strlen(k) == (size_t)(eq - p) && !std::strncmp(k, p, (size_t)(eq - p));
-            if (!ok && len) { std::fprintf(stderr, "magent-amd FATAL: MAGENT_TUNE: unknown entry \"%.*s\" (see magent_amd/csrc/tune.h)\n", (int)len, p); std::abort(); }
-            if (!e) break;
-            p = e + 1;
-        }
-    }
+    static const bool checked = tune_check_entries(s);
+    (void)checked;
     const size_t n = std::strlen(key);
     for (const char *p = s; *p;) {
         const char *e = std::strchr(p, ',');

@@ -55,13 +55,26 @@ def _typed(words, dtype, shape):
     return np.ascontiguousarray(words).view(dtype).reshape(shape)
 
 
-def play(scs, lib, flags, align_rows=None, log=None):
+def pool_stats(lib):
+    """env_cycle_pool_stats of engine library `lib`: [rounds, items, items run by workers, most threads in one round] of this process"""
+    from magent_amd import c_lib
+    out = (ctypes.c_longlong * 4)()
+    c_lib.load(lib).env_cycle_pool_stats(out)
+    return list(out)
+
+
+def play(scs, lib, flags, align_rows=None, log=None, n_threads=1, misalign=None):
     """`scs` in ONE EnvBatch on engine library `lib`, all their steps; flags[k][g]: environment k's group g is rendered as bf16 cells.
     align_rows None: every buffer an allocation of its own with one row of capacity to spare; a number: the packed layout -- per group ONE
     guarded buffer for each of views, feature rows, actions and rewards, laid out by EnvBatch.packed_offsets(nums, align_rows) and addressed
     through EnvBatch.packed_pointers; pad rows must come back holding the sentinel.  Guards are checked behind every cycle.
     log: a dict that receives per cycle "piped" (pipeline_stats()[6] of every environment), "renders" (render launches the profile counted
-    in this cycle), "observed" (groups observed), "aligned" (Env::observed_groups_ok's alignment condition restated on the pointers built).
+    in this cycle), "observed" (groups observed), "aligned" (Env::observed_groups_ok's alignment condition restated on the pointers built),
+    "pool" (pool_stats(lib) behind the cycle).
+    n_threads: the host threads env_cycle_many may use for the worlds that go alone -- a number, or a function cycle -> number.
+    misalign (align_rows None only): per environment None or an offset in float elements; every view buffer of that environment starts that
+    far behind a 16-byte boundary (helpers.guarded(offset_elems=...)), so Env::observed_groups_ok refuses the world and it goes alone,
+    through the call sequence.  Not for an environment with a cell entry: the engine aborts on a misaligned cell view.
     Returns one trajectory per scenario, in helpers.run_cycle_batch's form with cells%d in place of view%d where flags say so."""
     import torch
     built = [sc.build(lib) for sc in scs]
@@ -70,6 +83,8 @@ def play(scs, lib, flags, align_rows=None, log=None):
     dev = H.torch_device(envs[0], lib)
     batch = magent_amd.EnvBatch(envs, n_threads=1)
     batch.order_streams = not H.is_emu(lib)
+    assert misalign is None or (align_rows is None and not any(m and any(fl) for m, fl in zip(misalign, flags)))
+    shift = [0] * NE if misalign is None else [int(m or 0) for m in misalign]
     rss = [np.random.RandomState(sc.action_seed) for sc in scs]
     out, live = [[] for _ in scs], [True] * NE
     for env in envs:
@@ -98,8 +113,8 @@ def play(scs, lib, flags, align_rows=None, log=None):
         # ---- the buffers
         if align_rows is None:
             off = np.zeros((NE, NG), dtype=np.int64)
-            mk = lambda shape, dtype, on, n: H.guarded((n,) + tuple(shape), dtype, dev, 0, n + 1) if on else None
-            V = [[mk(*vrow(k, g), observe[k][g], nums[k][g]) for g in range(NG)] for k in range(NE)]
+            mk = lambda shape, dtype, on, n, shift=0: H.guarded((n,) + tuple(shape), dtype, dev, shift, n + 1) if on else None
+            V = [[mk(*vrow(k, g), observe[k][g], nums[k][g], shift[k]) for g in range(NG)] for k in range(NE)]
             F = [[mk(fspace[k][g], "float32", observe[k][g], nums[k][g]) for g in range(NG)] for k in range(NE)]
             R = [[mk((), "float32", paid[k][g], nums[k][g]) for g in range(NG)] for k in range(NE)]
             A = [[None if a is None else torch.from_numpy(a).to(dev) for a in acts[k]] for k in range(NE)]
@@ -131,8 +146,10 @@ def play(scs, lib, flags, align_rows=None, log=None):
         H.device_sync(lib)
         for env in envs:      # (a probe step's observations through the ordinary calls are render launches too: counted from here)
             env.profile_read("render")
+        batch.n_threads = n_threads(step) if callable(n_threads) else n_threads
         dones = batch.cycle(pv, pf, pa, pr, view_cells=cells if any(cells) else None)
         if log is not None:
+            log.setdefault("pool", []).append(pool_stats(lib))
             log.setdefault("piped", []).append([env.pipeline_stats()[6] for env in envs])
             log.setdefault("swept", []).append([env.pipeline_stats()[7] for env in envs])
             log.setdefault("renders", []).append([env.profile_read("render")[0] for env in envs])
@@ -166,6 +183,8 @@ def play(scs, lib, flags, align_rows=None, log=None):
                 if observe[k][g]:
                     if align_rows is None:
                         H.assert_guards_intact(V[k][g], tag + " view"); H.assert_guards_intact(F[k][g], tag + " feat")
+                        # (no output holds the sentinel: a world whose cycle was never run is named here, behind that cycle)
+                        H.assert_all_written(V[k][g], tag + " view"); H.assert_all_written(F[k][g], tag + " feat")
                     vw, fw = _segment(buf(V, k, g), o, n, tag), _segment(buf(F, k, g), o, n, tag)
                     if flags[k][g]:
                         rec["cells%d" % g] = _typed(vw, np.uint16, (n,) + vspace[k][g][:2] + (8,))
@@ -193,9 +212,9 @@ def play(scs, lib, flags, align_rows=None, log=None):
     return out
 
 
-def check(scs, lib, flags, what, align_rows=None, log=None):
+def check(scs, lib, flags, what, align_rows=None, log=None, n_threads=1, misalign=None):
     """play(...) against the oracle's trajectories, word for word"""
-    got = play(scs, lib, flags, align_rows, log)
+    got = play(scs, lib, flags, align_rows, log, n_threads, misalign)
     for sc, fl, g in zip(scs, flags, got):
         H.assert_same(with_cells(expectation(sc), fl), g, "%s (%s)" % (sc.name, what))
     return got
