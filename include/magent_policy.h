@@ -7,8 +7,8 @@
  * C entry point here (its model is a TensorFlow graph); the Python binding is magent_amd/builtin/torch_model/hip_policy.py.
  *
  * Further down: the same network in float32, the deep recurrent Q network's acting step in float32 and with bf16 operands
- * (policy_drqn_infer_f32, policy_drqn_infer), and the actor-critic's in float32 and with bf16 operands (policy_a2c_infer_f32,
- * policy_a2c_infer).
+ * (policy_drqn_infer_f32, policy_drqn_infer), the actor-critic's in float32 and with bf16 operands (policy_a2c_infer_f32,
+ * policy_a2c_infer), and the actor-critic's segmented form for packed batches (policy_a2c_infer_f32_seg, policy_a2c_infer_seg).
  *
  * All pointers are DEVICE pointers; the call enqueues two kernels on `stream` and returns.  Inputs are the engine's own
  * observation tensors (env_get_observation_device): view float[n][view_h][view_w][view_c], feature float[n][feat].
@@ -244,6 +244,39 @@ int policy_a2c_infer(const PolicyDqnShape *shape, const PolicyA2cWeights *weight
  * half of a k-step, nothing is converted); needs weights->dense_view_cells */
 int policy_a2c_infer_bf16(const PolicyDqnShape *shape, const PolicyA2cWeights *weights, const void *view_cells, const float *feature, int n,
                           const float *u, void *workspace, int *actions, float *policy, float *value, void *stream);
+
+/* ---- the segmented form of the actor-critic step, float32 and bf16: ONE call over n packed rows that belong to several independent
+ * groups of agents (the environments of an EnvBatch: packed_offsets / packed_segments), every CommNet mean taken inside the agent's own
+ * group.  The arguments of the plain entries, then the table: seg_begin int[n_seg], seg_count int[n_seg] -- HOST arrays, read before the
+ * call returns -- segment s is rows seg_begin[s] .. seg_begin[s] + seg_count[s] - 1.
+ *   others_i = (sum over the rows j of i's segment of h_j - h_i) / (count - 1), zeros for count == 1.  The column sums of segment s are
+ *   taken over blocks of 256 agents counted from the segment's OWN first row, in agent order, then over the blocks in order (no atomics):
+ *   the partition and order of the plain entry called on rows seg_begin[s] .. of view, feature and u alone, so every output of a
+ *   segment's rows has that call's bits, wherever the segment lies in the packed buffers.
+ *   A row in no segment (a pad row between two segments, a stale row behind a world's living agents) is a segment of one: others = 0.
+ *   Its outputs are written like any row's -- an action inside [0, n_action) -- and it enters no sum: a NaN there reaches nobody.
+ *   An empty segment (count == 0) is allowed and costs nothing; n_seg == 0: every row is alone.  Without use_comm the table is checked
+ *   and otherwise not looked at: the outputs are the plain entry's bits.  One segment (0, n) gives the plain entry's bits too.
+ * Refused (1 returned, nothing written) unless 0 <= n_seg <= POLICY_A2C_MAX_SEGMENTS, every seg_begin >= 0 and seg_count >= 0,
+ * seg_begin[s] + seg_count[s] <= n, and the segments ascend without overlap: seg_begin[s] >= seg_begin[s - 1] + seg_count[s - 1]; and
+ * for whatever the plain entry refuses.  A longer table is cut at segment boundaries into several calls (segments are independent).
+ * The table reaches the device as a kernel argument: no allocation, no copy from the host arrays, no wait.  With use_comm the call
+ * enqueues 10 kernels (the plain 9 and the one that spreads the table), fewer where no segment has an agent; without, the plain 3.
+ * The workspace (16-byte aligned) holds, beside the plain call's rows, one sum row per segment, at most n / 256 + n_seg partial rows
+ * and the row -> segment map: policy_a2c_*workspace_bytes_seg(shape, n, use_comm, n_seg). */
+#define POLICY_A2C_MAX_SEGMENTS 256
+int policy_a2c_f32_workspace_bytes_seg(const PolicyDqnShape *shape, int n, int use_comm, int n_seg, size_t *bytes);
+int policy_a2c_infer_f32_seg(const PolicyDqnShape *shape, const PolicyA2cWeightsF32 *weights, const float *view, const float *feature, int n,
+                             const float *u, void *workspace, int *actions, float *policy, float *value, void *stream,
+                             const int *seg_begin, const int *seg_count, int n_seg);
+int policy_a2c_workspace_bytes_seg(const PolicyDqnShape *shape, int n, int use_comm, int n_seg, size_t *bytes);
+int policy_a2c_infer_seg(const PolicyDqnShape *shape, const PolicyA2cWeights *weights, const float *view, const float *feature, int n,
+                         const float *u, void *workspace, int *actions, float *policy, float *value, void *stream,
+                         const int *seg_begin, const int *seg_count, int n_seg);
+/* the same with the views as the engine's bf16 cells, as policy_a2c_infer_bf16 */
+int policy_a2c_infer_bf16_seg(const PolicyDqnShape *shape, const PolicyA2cWeights *weights, const void *view_cells, const float *feature, int n,
+                              const float *u, void *workspace, int *actions, float *policy, float *value, void *stream,
+                              const int *seg_begin, const int *seg_count, int n_seg);
 
 #ifdef __cplusplus
 }

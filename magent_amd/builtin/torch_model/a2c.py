@@ -22,9 +22,9 @@ class _CommStep(nn.Module):
         self.C = nn.Linear(size, size, bias=False)
         self.H = nn.Linear(size, size, bias=False)
 
-    def forward(self, h, skip):
+    def forward(self, h, skip, alone=False):
         n = h.shape[0]
-        others = (h.sum(dim=0, keepdim=True) - h) / (n - 1) if n > 1 else torch.zeros_like(h)
+        others = (h.sum(dim=0, keepdim=True) - h) / (n - 1) if n > 1 and not alone else torch.zeros_like(h)
         return torch.tanh(self.C(others) + self.H(h) + skip)
 
 
@@ -38,13 +38,14 @@ class _ActorCritic(nn.Module):
         self.policy = nn.Linear(512, n_action)
         self.value = nn.Linear(512, 1)
 
-    def forward(self, view, feature):
+    def forward(self, view, feature, alone=False):
+        """alone: every row is a call of its own (the CommNet means are zeros)"""
         h = torch.cat([F.relu(self.dense_view(view.reshape(view.shape[0], -1))), F.relu(self.dense_emb(feature))], dim=1)
         h = F.relu(self.dense(h))
         if self.comm is not None:
             skip = h
             for step in self.comm:
-                h = step(h, skip)
+                h = step(h, skip, alone)
         policy = F.softmax(self.policy(h), dim=1).clamp(1e-10, 1 - 1e-10)
         return policy, self.value(h).squeeze(1)
 
@@ -93,20 +94,45 @@ class AdvantageActorCritic(BaseModel):
             return x.to(self.device, dtype)
         return torch.as_tensor(np.ascontiguousarray(x)).to(self.device, dtype)
 
+    def _policy_segments(self, view, feature, seg):
+        """the PyTorch network's probabilities [n][A] of a segmented call: the network per segment, and once, every row alone, over the
+        rows in no segment"""
+        n = view.shape[0]
+        policy = torch.empty((n, self.num_actions), device=view.device)
+        free = torch.ones(n, dtype=torch.bool)
+        for b, c in seg.tolist():
+            if c > 0:
+                policy[b:b + c] = self.net(view[b:b + c], feature[b:b + c])[0]
+                free[b:b + c] = False
+        idx = torch.nonzero(free).squeeze(1).to(view.device)
+        if len(idx):
+            policy[idx] = self.net(view[idx], feature[idx], alone=True)[0]
+        return policy
+
     @torch.no_grad()
-    def infer_action(self, raw_obs, ids, *args, **kwargs):
-        """one action per agent, sampled from the policy; raw_obs = (view [n,H,W,C], feature [n,F]), numpy or torch"""
+    def infer_action(self, raw_obs, ids, *args, segments=None, **kwargs):
+        """one action per agent, sampled from the policy; raw_obs = (view [n,H,W,C], feature [n,F]), numpy or torch.
+
+        segments: None, or an int array [n_seg][2] of (begin, count) rows for observations that pack several environments into one
+        buffer (EnvBatch.packed_segments): the CommNet means then run inside each segment, and a row in no segment (a pad row, a stale
+        row) acts alone.  The meaning is the same on the kernels and on the PyTorch path; without CommNet the table changes nothing."""
         view, feature = raw_obs[0], raw_obs[1]
         if len(view) == 0:
             return np.empty(0, dtype=np.int32)
+        if segments is not None:
+            from .hip_policy import check_segments
+            segments = check_segments(segments, len(view))
         if self._on_kernels(view, feature):
-            return self._hip.infer(view, feature)
+            return self._hip.infer(view, feature, segments=segments)
         if isinstance(view, torch.Tensor) and view.dtype == torch.bfloat16:
             # bf16 cells [n, H, W, 8] (channels, zeros, a constant 1) without the bf16 kernels: the channels go back to float32
             view = view[..., :self.view_space[-1]].float().contiguous()
             if self._on_kernels(view, feature):
-                return self._hip.infer(view, feature)
-        policy, _ = self.net(self._tensor(view), self._tensor(feature))
+                return self._hip.infer(view, feature, segments=segments)
+        if segments is not None and self.use_comm:
+            policy = self._policy_segments(self._tensor(view), self._tensor(feature), segments)
+        else:
+            policy, _ = self.net(self._tensor(view), self._tensor(feature))
         acts = torch.multinomial(policy, 1).squeeze(1).to(torch.int32)
         return acts if isinstance(view, torch.Tensor) else acts.cpu().numpy()
 

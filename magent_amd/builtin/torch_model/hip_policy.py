@@ -10,6 +10,7 @@ the caller's.  Setting `.dirty = True` forces a repack."""
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from ... import c_lib
@@ -447,6 +448,32 @@ class _A2cWeightsBf16(ctypes.Structure):
                 ("dense_emb_bias", ctypes.c_void_p), ("dense_bias", ctypes.c_void_p), ("head_bias", ctypes.c_void_p), ("use_comm", ctypes.c_int)]
 
 
+MAX_SEGMENTS = 256          # include/magent_policy.h: POLICY_A2C_MAX_SEGMENTS, the most segments of one C call
+
+
+def check_segments(segments, n):
+    """the (begin, count) table of a segmented A2C call over n rows as int64 [n_seg][2], validated as the library validates it
+    (include/magent_policy.h: policy_a2c_infer_f32_seg): ValueError naming the first offending segment"""
+    if isinstance(segments, torch.Tensor):
+        segments = segments.cpu().numpy()
+    seg = np.asarray(segments)
+    if seg.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if seg.ndim != 2 or seg.shape[1] != 2 or seg.dtype.kind not in "iu":
+        raise ValueError("segments is an integer array [n_seg][2] of (begin, count), not %s %s" % (seg.dtype, seg.shape))
+    seg = seg.astype(np.int64)
+    at = 0
+    for k, (b, c) in enumerate(seg.tolist()):
+        if b < 0 or c < 0:
+            raise ValueError("segment %d (begin %d, count %d): negative" % (k, b, c))
+        if b + c > n:
+            raise ValueError("segment %d (begin %d, count %d) ends past the call's %d rows" % (k, b, c, n))
+        if b < at:
+            raise ValueError("segment %d (begin %d, count %d) starts before the end of segment %d (row %d): segments ascend without overlap" % (k, b, c, k - 1, at))
+        at = b + c
+    return seg
+
+
 class _A2cPolicy(_Packed):
     """what the two A2C policies share: the constructor's check, the packing of the dense layers, the CommNet steps and the heads, and the
     chunked step.  A subclass names its entries of the library (`_abi`: supported, workspace_bytes, the kernels named in errors) and its
@@ -455,7 +482,14 @@ class _A2cPolicy(_Packed):
     The draw is the inverse CDF of one uniform number per agent (include/magent_policy.h: policy_a2c_infer_f32).  Without CommNet a call
     of n agents goes to the kernels `chunk` agents at a time (every agent's row is its own).  With CommNet the mean of the other agents
     spans the call, so the whole n goes to ONE C call whatever `chunk` is: the column sums are then taken over the same blocks of agents
-    in the same order, and the result does not depend on `chunk`.  `lib`: _Packed."""
+    in the same order, and the result does not depend on `chunk`.  `lib`: _Packed.
+
+    `segments` (infer): an int array [n_seg][2] of (begin, count) rows -- the environments of a packed EnvBatch buffer
+    (EnvBatch.packed_segments).  Every CommNet mean then runs over the rows of the agent's own segment; a row in no segment (pad, stale)
+    is alone: others = 0, its action is in range, nobody's mean sees it.  A segment's outputs have the bits of a plain call on that
+    segment's rows alone.  The call still goes to the library whole -- one C call per MAX_SEGMENTS segments, cut at segment boundaries
+    (segments are independent; the rows between two cuts go with the call in front).  Without CommNet the table is validated and changes
+    nothing.  None: the plain call."""
     _source = "net"
     _abi = _struct = None
 
@@ -494,8 +528,8 @@ class _A2cPolicy(_Packed):
         w.use_comm = int(self.use_comm)
         self._set_packed(t, w, stamp)
 
-    def _step(self, entry, view, feature, u, want_policy, want_value):
-        """the library's `entry` on every chunk of the call (CommNet: on the whole call)"""
+    def _step(self, entry, view, feature, u, want_policy, want_value, segments=None):
+        """the library's `entry` on every chunk of the call (CommNet: on the whole call; with `segments`, its segmented form)"""
         assert view.device == feature.device and view.device.type == self.device.type
         assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32 and view.shape[0] == feature.shape[0]
         call = getattr(self._lib, entry)
@@ -508,6 +542,12 @@ class _A2cPolicy(_Packed):
         actions = torch.empty(n, dtype=torch.int32, device=dev)
         policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
         value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
+        out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
+        if segments is not None:
+            seg = check_segments(segments, n)
+            if self.use_comm:
+                self._step_segments(entry + "_seg", seg, view, feature, u, actions, policy, value)
+                return out if len(out) > 1 else actions
         chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
         self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, chunk), int(self.use_comm))
         stream = _stream(dev)
@@ -515,8 +555,30 @@ class _A2cPolicy(_Packed):
             ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
             self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
             _ptr(value[beg:] if want_value else None), stream))
-        out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
         return out if len(out) > 1 else actions
+
+    def _step_segments(self, entry, seg, view, feature, u, actions, policy, value):
+        """the segmented `entry` over the validated table `seg`: one C call per MAX_SEGMENTS segments, each over the rows from its first
+        segment's begin (the first call: row 0) to the next call's (the last: n)"""
+        call, n = getattr(self._lib, entry), view.shape[0]
+        cuts = list(range(0, len(seg), MAX_SEGMENTS)) or [0]
+        pieces = []
+        for k in cuts:
+            part = seg[k:k + MAX_SEGMENTS]
+            r0 = 0 if k == 0 else int(part[0, 0])
+            r1 = n if k + MAX_SEGMENTS >= len(seg) else int(seg[k + MAX_SEGMENTS, 0])
+            if r1 > r0:
+                begin = (ctypes.c_int32 * max(len(part), 1))(*(part[:, 0] - r0).tolist())
+                count = (ctypes.c_int32 * max(len(part), 1))(*part[:, 1].tolist())
+                pieces.append((r0, r1 - r0, begin, count, len(part)))
+                self._grow_work(view.device, getattr(self._lib, self._abi[1] + "_seg"), r1 - r0, 1, len(part))
+        stream = _stream(view.device)
+        for r0, m, begin, count, n_seg in pieces:
+            rc = call(ctypes.byref(self.shape), ctypes.byref(self._w), view[r0:].data_ptr(), feature[r0:].data_ptr(), m, u[r0:].data_ptr(),
+                      self._work.data_ptr(), actions[r0:].data_ptr(), _ptr(None if policy is None else policy[r0:]),
+                      _ptr(None if value is None else value[r0:]), stream, begin, count, n_seg)
+            if rc != 0:
+                raise RuntimeError("%s failed (%d)" % (entry, rc))
 
 
 class HipA2cPolicyF32(_A2cPolicy):
@@ -530,12 +592,12 @@ class HipA2cPolicyF32(_A2cPolicy):
         self._pack_dense(fragment_order_f32, 8)
 
     @torch.no_grad()
-    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
+    def infer(self, view, feature, u=None, want_policy=False, want_value=False, segments=None):
         """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
-        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
-        probabilities [n][A] and / or the values [n] if asked for"""
+        torch.rand from torch's generator; segments: None, or the (begin, count) table of a packed buffer (_A2cPolicy).  Enqueues the step
+        on torch's current stream; returns int32 actions [n], followed by the probabilities [n][A] and / or the values [n] if asked for"""
         assert view.dtype == torch.float32 and tuple(view.shape[1:]) == (self.shape.view_h, self.shape.view_w, self.shape.view_c)
-        return self._step("policy_a2c_infer_f32", view, feature, u, want_policy, want_value)
+        return self._step("policy_a2c_infer_f32", view, feature, u, want_policy, want_value, segments)
 
 
 class HipA2cPolicy(_A2cPolicy):
@@ -561,11 +623,11 @@ class HipA2cPolicy(_A2cPolicy):
         self._pack_dense(fragment_order, 16, self._pack_cells)
 
     @torch.no_grad()
-    def infer(self, view, feature, u=None, want_policy=False, want_value=False):
+    def infer(self, view, feature, u=None, want_policy=False, want_value=False, segments=None):
         """view float32 [n][H][W][C] -- or bfloat16 [n][H][W][8], the engine's cells (GridWorld.get_observation_device_bf16), where the
         shape has them --, feature float32 [n][F] (contiguous, on the policy's device); u float32 [n] uniform in [0, 1), or None:
-        torch.rand from torch's generator.  Enqueues the step on torch's current stream; returns int32 actions [n], followed by the
-        probabilities [n][A] and / or the values [n] if asked for"""
+        torch.rand from torch's generator; segments: None, or the (begin, count) table of a packed buffer (_A2cPolicy).  Enqueues the step
+        on torch's current stream; returns int32 actions [n], followed by the probabilities [n][A] and / or the values [n] if asked for"""
         cells16, s = view.dtype == torch.bfloat16, self.shape
         if cells16:
             if not self.cells:
@@ -573,4 +635,4 @@ class HipA2cPolicy(_A2cPolicy):
             assert tuple(view.shape[1:]) == (s.view_h, s.view_w, 8)
         else:
             assert view.dtype == torch.float32 and tuple(view.shape[1:]) == (s.view_h, s.view_w, s.view_c)
-        return self._step("policy_a2c_infer_bf16" if cells16 else "policy_a2c_infer", view, feature, u, want_policy, want_value)
+        return self._step("policy_a2c_infer_bf16" if cells16 else "policy_a2c_infer", view, feature, u, want_policy, want_value, segments)

@@ -79,6 +79,12 @@ POLICY_ABI = [
     ("policy_a2c_workspace_bytes", [_vp, _i, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_a2c_infer", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("policy_a2c_infer_bf16", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the segmented forms: the plain arguments, then seg_begin, seg_count (host int arrays) and n_seg
+    ("policy_a2c_f32_workspace_bytes_seg", [_vp, _i, _i, _i, _c.POINTER(_c.c_size_t)]),
+    ("policy_a2c_infer_f32_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
+    ("policy_a2c_workspace_bytes_seg", [_vp, _i, _i, _i, _c.POINTER(_c.c_size_t)]),
+    ("policy_a2c_infer_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
+    ("policy_a2c_infer_bf16_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
 ]
 # include/magent_runtime_api.h PART 3, the rule-based actors: (name, restype, argtypes).  A table of its own, bound only where
 # the library exports it (the CPU checkers under oracle/ do not; `has_actor_api` says whether this one does).

@@ -34,6 +34,10 @@
 // k_a2c_colsum_part_bf16 + k_a2c_colsum_bf16 : the f32 path's column sums (policy_f32_dev.h: colsum_part, colsum_blocks) over the bf16
 //   rows, added in float32 -- partial sums over blocks of 256 agents in agent order, then the blocks in block order.  No atomics: the
 //   sums are a function of the call's inputs alone.
+// The segmented call (policy_a2c_infer_seg, policy_a2c_infer_bf16_seg): k_a2c_segmap_bf16, k_a2c_colsum_part_seg_bf16 +
+//   k_a2c_colsum_seg_bf16 as in policy_a2c_f32.hip (the same bodies), and k_a2c_layer_bf16<true, true>: the sum row, the divisor and
+//   `alone` per lane.  Its sums do not go through LDS (a workgroup may touch as many segments as it has agents): a lane loads the eight
+//   float32 sums of a k-step from its segment's row with the k-step's operands, through three register buffers of ONE k-step.
 // k_a2c_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512 (policy_bf16_dev.h: head_gemm512_bf16, shared with
 //   k_drqn_head_bf16; the operand as stored), float32 biases, then policy_f32_dev.h: policy_epilogue, the f32 head's own softmax, clamp
 //   and draw.  The workspace layout is policy_host.h: a2c_layout, the f32 path's with 2-byte row elements.
@@ -190,14 +194,27 @@ struct LayerArgs {
     const float *bias;        // [512] (dense)
     bf16_t *out;              // [n][512]
     int n, groups;
+    const int *row_seg;       // [n], seg_tab [n_seg][4]: the segmented call's maps (policy_f32_dev.h: seg_map); `sum` is then [n_seg][512]
+    const int *seg_tab;
 };
 
-struct XOp { bf16x8 a, w[GEMM_TILES]; };      // one k-step: the lane's 16 bytes of the row as stored, four weight fragments
+// one k-step: the lane's 16 bytes of the row as stored, four weight fragments; <true>, the segmented step's: and the eight column sums of
+// the k-step, loaded with the operands from the lane's segment's row of the table
+template <bool SEG> struct XOp { bf16x8 a, w[GEMM_TILES]; };
+template <> struct XOp<true> { bf16x8 a, w[GEMM_TILES]; f32x4 s[2]; };
+__device__ __forceinline__ void load_sums(XOp<false> &, const f32x4 *, int) {}
+__device__ __forceinline__ void load_sums(XOp<true> &d, const f32x4 *gsp, int s) { d.s[0] = gsp[4 * s]; d.s[1] = gsp[4 * s + 1]; }
+__device__ __forceinline__ void held_sums(const XOp<false> &, f32x4 &, f32x4 &) {}
+__device__ __forceinline__ void held_sums(const XOp<true> &d, f32x4 &lo, f32x4 &hi) { lo = d.s[0]; hi = d.s[1]; }
 
-template <bool COMM>
+// <COMM, SEG>: SEG is the CommNet step of a segmented call -- the sum row, the divisor and `alone` are the lane's agent's segment's.  The
+// call's single sum row goes through LDS; a workgroup of 256 agents of a segmented call may touch as many segments as it has agents, so
+// there each lane loads its own segment's sums from global memory (n_seg rows of 2 KB: L2) beside the operands of the same k-step.
+template <bool COMM, bool SEG = false>
 __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
-    __shared__ __attribute__((aligned(16))) float s_sum[HID];
-    if (COMM) {                                                  // (before any wave leaves: GEMM_THREADS == HID)
+    static_assert(COMM || !SEG, "only the CommNet step has a segmented form");
+    __shared__ __attribute__((aligned(16))) float s_sum[SEG ? 4 : HID];
+    if (COMM && !SEG) {                                          // (before any wave leaves: GEMM_THREADS == HID)
         s_sum[threadIdx.x] = A.sum[threadIdx.x];
         __syncthreads();
     }
@@ -210,36 +227,53 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
     const int T0 = tg * GEMM_TILES;
     const bf16x8 *xp = A.in + (size_t)agent * (HID / 8) + g;                  // k-step s: xp[2 s] = in[16 s + 8 g .. + 7]
     const bf16x8 *wp = A.w + (size_t)T0 * 64 + l;                             // (k-step s, tile T0 + t) at wp[(s * 16 + t) * 64]
-    const float others_div = (float)(A.n - 1);
-    const bool alone = A.n == 1;
+    float others_div = (float)(A.n - 1);
+    bool alone = A.n == 1;
+    const f32x4 *gsp = nullptr;                                  // SEG: the lane's segment's sum row, k-step s at gsp[4 s], gsp[4 s + 1]
+    if constexpr (SEG) {                                         // per lane: a wave may straddle any number of segments
+        const magent_amd::f32::SegOfRow so = magent_amd::f32::seg_of_row(A.row_seg, A.seg_tab, agent);
+        gsp = (const f32x4 *)(A.sum + (size_t)so.sum_row * HID) + 2 * g;
+        others_div = so.others_div;
+        alone = so.alone;
+    }
     f32x16 acc[GEMM_TILES];
 #pragma unroll
     for (int t = 0; t < GEMM_TILES; t++) acc[t] = f32x16{0};
-    XOp op[3][LY_CHUNK];
+    // k-steps per register buffer: the segmented step's buffers also hold the sums, eight float32 per k-step, and three buffers of two
+    // k-steps no longer fit 256 VGPRs beside the accumulators (38 spilled) -- it runs three buffers of one k-step
+    constexpr int CH = SEG ? 1 : LY_CHUNK;
+    typedef XOp<SEG> Op;
+    Op op[3][CH];
     auto phase = [&](auto is_others) __attribute__((always_inline)) {
         constexpr bool O = decltype(is_others)::value;
         const bf16x8 *wph = wp + ((COMM && !O) ? (size_t)KSTEPS * 16 * 64 : 0);
         int at = 0;                                              // the chunk `run` is at (ring3 is fully unrolled: a constant)
-        auto load = [&](int c, XOp (&d)[LY_CHUNK]) __attribute__((always_inline)) {
+        auto load = [&](int c, Op (&d)[CH]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int k = 0; k < LY_CHUNK; k++) {
-                const int s = c * LY_CHUNK + k;
+            for (int k = 0; k < CH; k++) {
+                const int s = c * CH + k;
                 d[k].a = xp[2 * s];
+                if (SEG && O) load_sums(d[k], gsp, s);
 #pragma unroll
                 for (int t = 0; t < GEMM_TILES; t++) d[k].w[t] = wph[((size_t)s * 16 + t) * 64];
             }
         };
-        auto run = [&](const XOp (&d)[LY_CHUNK]) __attribute__((always_inline)) {
+        auto run = [&](const Op (&d)[CH]) __attribute__((always_inline)) {
 #pragma unroll
-            for (int k = 0; k < LY_CHUNK; k++) {
+            for (int k = 0; k < CH; k++) {
                 bf16x8 b = d[k].a;
                 if (O) {                                         // the mean of the OTHER agents, float32, then rounded as the operand
-                    const float *sp = s_sum + 16 * (at * LY_CHUNK + k) + 8 * g;
+                    f32x4 slo, shi;
+                    if (SEG) held_sums(d[k], slo, shi);
+                    else {
+                        const float *sp = s_sum + 16 * (at * CH + k) + 8 * g;
+                        slo = *(const f32x4 *)sp; shi = *(const f32x4 *)(sp + 4);
+                    }
                     const u32x4 raw = __builtin_bit_cast(u32x4, d[k].a);
                     f32x4 lo = widen(u32x2{raw[0], raw[1]}), hi = widen(u32x2{raw[2], raw[3]});
                     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-                    lo = alone ? zero : (*(const f32x4 *)sp - lo) / others_div;
-                    hi = alone ? zero : (*(const f32x4 *)(sp + 4) - hi) / others_div;
+                    lo = alone ? zero : (slo - lo) / others_div;
+                    hi = alone ? zero : (shi - hi) / others_div;
                     b = round_bf16x8(lo, hi);
                 }
 #pragma unroll
@@ -247,7 +281,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
             }
             at++;
         };
-        ring3<KSTEPS / LY_CHUNK>(op, load, run);
+        ring3<KSTEPS / CH>(op, load, run);
     };
     if (COMM) phase(std::integral_constant<bool, true>{});
     phase(std::integral_constant<bool, false>{});
@@ -272,6 +306,17 @@ __global__ void __launch_bounds__(HID) k_a2c_colsum_part_bf16(const bf16_t *h, i
     magent_amd::f32::colsum_part(n, part, [&](size_t i) { return bf_lo(h[i]); });
 }
 __global__ void __launch_bounds__(HID) k_a2c_colsum_bf16(const float *part, int n_blocks, float *sum) { magent_amd::f32::colsum_blocks(part, n_blocks, sum); }
+// the segmented call's: the maps (policy_f32_dev.h: seg_map), then the sums per segment (colsum_part_seg, colsum_blocks_seg)
+constexpr int SM_THREADS = 256;
+__global__ void __launch_bounds__(SM_THREADS) k_a2c_segmap_bf16(magent_amd::A2cSegTable t, int n, int *row_seg, int *seg_tab, int *blk_map) {
+    magent_amd::f32::seg_map(t, n, row_seg, seg_tab, blk_map);
+}
+__global__ void __launch_bounds__(HID) k_a2c_colsum_part_seg_bf16(const bf16_t *h, const int *seg_tab, const int *blk_map, float *part) {
+    magent_amd::f32::colsum_part_seg(seg_tab, blk_map, part, [&](size_t i) { return bf_lo(h[i]); });
+}
+__global__ void __launch_bounds__(HID) k_a2c_colsum_seg_bf16(const float *part, const int *seg_tab, float *sum) {
+    magent_amd::f32::colsum_blocks_seg(part, seg_tab, sum);
+}
 
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
 constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES;
@@ -303,11 +348,12 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_bf16(PHeadArgs A) {
 
 // ---------------------------------------------------------------------------------------------------- the workspace
 static magent_amd::A2cLayout layout(int n, bool comm) { return magent_amd::a2c_layout(n, comm, sizeof(bf16_t)); }      // policy_host.h
+static magent_amd::A2cSegLayout seg_layout(int n, bool comm, int n_seg) { return magent_amd::a2c_seg_layout(n, comm, sizeof(bf16_t), n_seg); }
 
 static bool cells_supported(const PolicyDqnShape *s) { return s->view_c <= 7 && 8LL * s->view_h * s->view_w <= TR_KMAX; }
 
 static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view, bool cells, const float *feat, int n, const float *u,
-                     void *workspace, int *actions, float *policy, float *value, void *stream) {
+                     void *workspace, int *actions, float *policy, float *value, void *stream, const magent_amd::A2cSegTable *seg = nullptr) {
     if (!s || !w || !policy_a2c_supported(s) || (cells && !cells_supported(s))) return 1;
     const bool comm = w->use_comm != 0;
     if (!(cells ? w->dense_view_cells : w->dense_view) || !w->dense_emb || !w->dense || !w->head || !w->dense_view_bias || !w->dense_emb_bias ||
@@ -317,10 +363,12 @@ static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const v
     if (!view || !feat || !u || !actions || !workspace) return 1;
     if ((uintptr_t)workspace & 15) return 1;                     // (rows are read as 16-byte units)
     if (cells && ((uintptr_t)view & 15)) return 1;               // (a cell is one 16-byte load)
+    if (!comm) seg = nullptr;                                    // (every row is its own: the plain call)
     hipStream_t st = (hipStream_t)stream;
     magent_amd::StreamDevice on(st);
     if (!on.ok) return 2;
     const magent_amd::A2cLayout L = layout(n, comm);
+    const magent_amd::A2cSegLayout S = seg_layout(n, comm, seg ? seg->n_seg : 0);      // (x, h0 and h1 lie where L has them)
     char *ws = (char *)workspace;
     bf16_t *x = (bf16_t *)(ws + L.x), *h0 = (bf16_t *)(ws + L.h0);
     const int groups = (n + 32 * GEMM_WAVES - 1) / (32 * GEMM_WAVES);
@@ -337,14 +385,26 @@ static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const v
     hipLaunchKernelGGL(k_a2c_layer_bf16<false>, lgrid, dim3(GEMM_THREADS), 0, st, D);
     const bf16_t *h = h0;
     if (comm) {
-        float *part = (float *)(ws + L.part), *sum = (float *)(ws + L.sum);
+        float *part = (float *)(ws + (seg ? S.part : L.part)), *sum = (float *)(ws + (seg ? S.sum : L.sum));
         bf16_t *outs[2] = {x, (bf16_t *)(ws + L.h1)};            // (x is free once the dense layer has read it)
+        int *row_seg = (int *)(ws + S.row_seg), *seg_tab = (int *)(ws + S.seg_tab), *blk_map = (int *)(ws + S.blk_map);
+        const int seg_blocks = seg ? magent_amd::a2c_seg_blocks(*seg) : 0;
+        if (seg) hipLaunchKernelGGL(k_a2c_segmap_bf16, dim3(seg->n_seg > 0 ? seg->n_seg : 1), dim3(SM_THREADS), 0, st, *seg, n, row_seg, seg_tab, blk_map);
         for (int step = 0; step < 2; step++) {
-            hipLaunchKernelGGL(k_a2c_colsum_part_bf16, dim3(L.n_blocks), dim3(HID), 0, st, h, n, part);
-            hipLaunchKernelGGL(k_a2c_colsum_bf16, dim3(1), dim3(HID), 0, st, (const float *)part, L.n_blocks, sum);
             LayerArgs C{};
             C.in = (const bf16x8 *)h; C.sum = sum; C.skip = h0; C.w = (const bf16x8 *)w->comm[step]; C.out = outs[step]; C.n = n; C.groups = groups;
-            hipLaunchKernelGGL(k_a2c_layer_bf16<true>, lgrid, dim3(GEMM_THREADS), 0, st, C);
+            if (seg) {
+                if (seg_blocks > 0) {                            // (no agent in any segment: no sum is read)
+                    hipLaunchKernelGGL(k_a2c_colsum_part_seg_bf16, dim3(seg_blocks), dim3(HID), 0, st, h, (const int *)seg_tab, (const int *)blk_map, part);
+                    hipLaunchKernelGGL(k_a2c_colsum_seg_bf16, dim3(seg->n_seg), dim3(HID), 0, st, (const float *)part, (const int *)seg_tab, sum);
+                }
+                C.row_seg = row_seg; C.seg_tab = seg_tab;
+                hipLaunchKernelGGL((k_a2c_layer_bf16<true, true>), lgrid, dim3(GEMM_THREADS), 0, st, C);
+            } else {
+                hipLaunchKernelGGL(k_a2c_colsum_part_bf16, dim3(L.n_blocks), dim3(HID), 0, st, h, n, part);
+                hipLaunchKernelGGL(k_a2c_colsum_bf16, dim3(1), dim3(HID), 0, st, (const float *)part, L.n_blocks, sum);
+                hipLaunchKernelGGL(k_a2c_layer_bf16<true>, lgrid, dim3(GEMM_THREADS), 0, st, C);
+            }
             h = outs[step];
         }
     }
@@ -379,6 +439,28 @@ int policy_a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const f
 int policy_a2c_infer_bf16(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view_cells, const float *feat, int n, const float *u,
                           void *workspace, int *actions, float *policy, float *value, void *stream) {
     return a2c_infer(s, w, view_cells, true, feat, n, u, workspace, actions, policy, value, stream);
+}
+
+int policy_a2c_workspace_bytes_seg(const PolicyDqnShape *s, int n, int use_comm, int n_seg, size_t *bytes) {
+    (void)s;
+    *bytes = seg_layout(n < 0 ? 0 : n, use_comm != 0, n_seg < 0 ? 0 : n_seg).bytes;
+    return 0;
+}
+
+int policy_a2c_infer_seg(const PolicyDqnShape *s, const PolicyA2cWeights *w, const float *view, const float *feat, int n, const float *u,
+                         void *workspace, int *actions, float *policy, float *value, void *stream, const int *seg_begin,
+                         const int *seg_count, int n_seg) {
+    magent_amd::A2cSegTable t;
+    if (!magent_amd::a2c_seg_table(seg_begin, seg_count, n_seg, n, &t)) return 1;
+    return a2c_infer(s, w, view, false, feat, n, u, workspace, actions, policy, value, stream, &t);
+}
+
+int policy_a2c_infer_bf16_seg(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view_cells, const float *feat, int n,
+                              const float *u, void *workspace, int *actions, float *policy, float *value, void *stream,
+                              const int *seg_begin, const int *seg_count, int n_seg) {
+    magent_amd::A2cSegTable t;
+    if (!magent_amd::a2c_seg_table(seg_begin, seg_count, n_seg, n, &t)) return 1;
+    return a2c_infer(s, w, view_cells, true, feat, n, u, workspace, actions, policy, value, stream, &t);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 //   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, head_gemm512_bf16)
 //   state_row                                        the id table's look-up (k_drqn_gru_f32, k_drqn_gru_bf16)
 //   colsum_part, colsum_blocks                       the CommNet column sums' bodies (the four k_a2c_colsum* kernels)
+//   seg_map, colsum_part_seg, colsum_blocks_seg, seg_of_row   the segmented A2C call's maps and sums (both k_a2c_segmap_*, the four *_seg_* kernels)
 // The bf16 files take their float32 side from here too (policy_bf16_dev.h includes this header): policy.hip the vector types, out_of
 // and q_before; policy_drqn_bf16.hip out_of, sigmoid, q_epilogue and state_row (its gates, blend and epilogue are float32);
 // policy_a2c_bf16.hip out_of, relu, policy_epilogue and the column sums.
@@ -309,6 +310,52 @@ __device__ __forceinline__ void colsum_blocks(const float *part, int n_blocks, f
 #pragma unroll 32
     for (int b = 0; b < n_blocks; b++) s += part[(size_t)b * A2C_HID + c];
     sum[c] = s;
+}
+
+// The same sums per segment of a segmented call (policy_host.h: A2cSegTable, a2c_seg_layout).  Segment s is cut into blocks of
+// A2C_CS_BLOCK agents counted from ITS first row; a block is added in agent order, a segment's blocks in block order: the partition and
+// the order of colsum_part / colsum_blocks on that segment alone, so the sums have that call's bits.
+// seg_map: workgroup s (of max(n_seg, 1), any size) writes segment s's entry of seg_tab, its blocks' entries of blk_map, and row_seg of
+// the segment's rows and of the rows between it and the next segment (-1; workgroup 0 also the rows in front of the first segment).
+__device__ __forceinline__ void seg_map(const A2cSegTable &t, int n, int *row_seg, int *seg_tab, int *blk_map) {
+    const int s = blockIdx.x, tid = threadIdx.x, step = blockDim.x;
+    if (t.n_seg == 0) {
+        for (int r = tid; r < n; r += step) row_seg[r] = -1;
+        return;
+    }
+    const int beg = t.begin[s], cnt = t.count[s], nblk = (cnt + A2C_CS_BLOCK - 1) / A2C_CS_BLOCK;
+    const int next = s + 1 < t.n_seg ? t.begin[s + 1] : n;
+    int blk0 = 0;
+    for (int k = 0; k < s; k++) blk0 += (t.count[k] + A2C_CS_BLOCK - 1) / A2C_CS_BLOCK;
+    if (tid == 0) {
+        seg_tab[4 * s] = beg; seg_tab[4 * s + 1] = cnt; seg_tab[4 * s + 2] = blk0; seg_tab[4 * s + 3] = nblk;
+    }
+    for (int b = tid; b < nblk; b += step) { blk_map[2 * (blk0 + b)] = s; blk_map[2 * (blk0 + b) + 1] = b; }
+    for (int r = (s == 0 ? 0 : beg) + tid; r < next; r += step) row_seg[r] = (r >= beg && r < beg + cnt) ? s : -1;
+}
+// workgroup b of sum over s of ceil(count_s / A2C_CS_BLOCK): the partial row of block blk_map[b]
+template <class At>
+__device__ __forceinline__ void colsum_part_seg(const int *seg_tab, const int *blk_map, float *part, const At &at) {
+    const int c = threadIdx.x, s = blk_map[2 * blockIdx.x], k = blk_map[2 * blockIdx.x + 1];
+    const int beg = seg_tab[4 * s] + k * A2C_CS_BLOCK, end = min(beg + A2C_CS_BLOCK, seg_tab[4 * s] + seg_tab[4 * s + 1]);
+    float sum = 0.0f;
+#pragma unroll 16
+    for (int a = beg; a < end; a++) sum += at((size_t)a * A2C_HID + c);
+    part[(size_t)blockIdx.x * A2C_HID + c] = sum;
+}
+// workgroup s: segment s's blocks in block order -> sum[s][A2C_HID] (an empty segment: zeros, never read)
+__device__ __forceinline__ void colsum_blocks_seg(const float *part, const int *seg_tab, float *sum) {
+    const int s = blockIdx.x;
+    colsum_blocks(part + (size_t)seg_tab[4 * s + 2] * A2C_HID, seg_tab[4 * s + 3], sum + (size_t)s * A2C_HID);
+}
+// what a lane of the segmented CommNet layer takes from its agent's segment: the sum row, the divisor count - 1 and whether the agent is
+// alone (count == 1, or a row in no segment: row_seg < 0 -- then the sum row is segment 0's, loaded and not used)
+struct SegOfRow { int sum_row; float others_div; bool alone; };
+__device__ __forceinline__ SegOfRow seg_of_row(const int *row_seg, const int *seg_tab, int agent) {
+    const int s = row_seg[agent];
+    if (s < 0) return SegOfRow{0, 1.0f, true};
+    const int cnt = seg_tab[4 * s + 1];
+    return SegOfRow{s, (float)(cnt - 1), cnt == 1};
 }
 
 // The DQN's trunk for the DRQN: k_dqn_conv_f32, then k_dqn_head_f32 stopped after its hidden layer, which it stores as

@@ -703,7 +703,9 @@ class EnvBatch(object):
     actions and float32 rewards all keep the alignment; packed_pointers() turns one base tensor per group into cycle()'s pointer array.  The
     <= 3 pad rows between two segments are never written by the engine -- the caller fills the buffers once -- and what a policy computes
     for them is ignored: the engine reads each segment's n actions only.  A network whose rows talk to each other -- the A2C's CommNet
-    averages over all rows of a call -- would average over every environment of a packed buffer: call it per environment, on the segment."""
+    averages over the rows of a call -- needs to know where one environment ends: packed_segments() gives each group's (begin, count)
+    table, and AdvantageActorCritic.infer_action(..., segments=table) keeps every mean inside its environment in ONE call per side; pad
+    rows and the stale rows behind a world's living agents act alone and enter no mean."""
 
     def __init__(self, envs, n_threads=8):
         self.envs, self.n_threads = list(envs), n_threads
@@ -775,6 +777,14 @@ class EnvBatch(object):
         arr = (ctypes.c_void_p * addr.size)()
         ctypes.memmove(arr, addr.ctypes.data, addr.nbytes)
         return arr
+
+    def packed_segments(self, offsets, nums=None):
+        """per group the int32 table [n_env][2] of (begin, count) rows of a packed layout: begin = offsets[e][g] (packed_offsets()'s, fixed
+        when the buffers were made), count = nums[e][g], default self.nums_array() -- the agents living NOW, so the stale rows behind them
+        are in no segment.  What a policy whose rows talk to each other takes as `segments`.  Host arithmetic only."""
+        off = np.asarray(offsets, dtype=np.int64).reshape(len(self.envs), self.n_group)
+        n = np.asarray(self.nums_array() if nums is None else nums, dtype=np.int64).reshape(len(self.envs), self.n_group)
+        return [np.stack([off[:, g], n[:, g]], axis=1).astype(np.int32) for g in range(self.n_group)]
 
     def nums(self):
         """agent counts [env][group] (host mirror, no device work)"""
