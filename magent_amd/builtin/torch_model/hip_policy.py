@@ -532,7 +532,6 @@ class _A2cPolicy(_Packed):
         """the library's `entry` on every chunk of the call (CommNet: on the whole call; with `segments`, its segmented form)"""
         assert view.device == feature.device and view.device.type == self.device.type
         assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32 and view.shape[0] == feature.shape[0]
-        call = getattr(self._lib, entry)
         if self.stale():
             self.pack()
         n, dev, A = view.shape[0], view.device, self.shape.n_action
@@ -543,27 +542,33 @@ class _A2cPolicy(_Packed):
         policy = torch.empty((n, A), dtype=torch.float32, device=dev) if want_policy else None
         value = torch.empty(n, dtype=torch.float32, device=dev) if want_value else None
         out = (actions,) + ((policy,) if want_policy else ()) + ((value,) if want_value else ())
-        if segments is not None:
-            seg = check_segments(segments, n)
-            if self.use_comm:
-                self._step_segments(entry + "_seg", seg, view, feature, u, actions, policy, value)
-                return out if len(out) > 1 else actions
-        chunk = n if self.use_comm else self.chunk                    # (CommNet: the call goes to the library whole)
-        self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, chunk), int(self.use_comm))
         stream = _stream(dev)
-        self._chunked(entry, n, chunk, lambda beg, m: call(
-            ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, u[beg:].data_ptr(),
-            self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(policy[beg:] if want_policy else None),
-            _ptr(value[beg:] if want_value else None), stream))
+
+        def piece(name, r0, m, *table):      # the library's `name` on rows r0 .. r0 + m - 1; table: a segmented entry's begin, count, n_seg
+            rc = getattr(self._lib, name)(
+                ctypes.byref(self.shape), ctypes.byref(self._w), view[r0:].data_ptr(), feature[r0:].data_ptr(), m, u[r0:].data_ptr(),
+                self._work.data_ptr(), actions[r0:].data_ptr(), _ptr(policy[r0:] if want_policy else None),
+                _ptr(value[r0:] if want_value else None), stream, *table)
+            if rc != 0:
+                raise RuntimeError("%s failed (%d)" % (name, rc))
+
+        seg = None if segments is None else check_segments(segments, n)
+        if seg is not None and self.use_comm:
+            for p in self._segment_pieces(seg, n, dev):
+                piece(entry + "_seg", *p)
+        else:                                                         # the plain call: the piece (0, chunk) without a table, and so on
+            chunk = n if self.use_comm else self.chunk                # (CommNet: the call goes to the library whole)
+            self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, chunk), int(self.use_comm))
+            for beg in range(0, n, max(chunk, 1)):
+                piece(entry, beg, min(chunk, n - beg))
         return out if len(out) > 1 else actions
 
-    def _step_segments(self, entry, seg, view, feature, u, actions, policy, value):
-        """the segmented `entry` over the validated table `seg`: one C call per MAX_SEGMENTS segments, each over the rows from its first
-        segment's begin (the first call: row 0) to the next call's (the last: n)"""
-        call, n = getattr(self._lib, entry), view.shape[0]
-        cuts = list(range(0, len(seg), MAX_SEGMENTS)) or [0]
+    def _segment_pieces(self, seg, n, dev):
+        """the segmented entry's calls over the validated table `seg`: (first row, rows, begin, count, n_seg), one per MAX_SEGMENTS
+        segments, each over the rows from its first segment's begin (the first call: row 0) to the next call's (the last: n); the
+        workspace is grown to the largest"""
         pieces = []
-        for k in cuts:
+        for k in (range(0, len(seg), MAX_SEGMENTS) or [0]):
             part = seg[k:k + MAX_SEGMENTS]
             r0 = 0 if k == 0 else int(part[0, 0])
             r1 = n if k + MAX_SEGMENTS >= len(seg) else int(seg[k + MAX_SEGMENTS, 0])
@@ -571,19 +576,13 @@ class _A2cPolicy(_Packed):
                 begin = (ctypes.c_int32 * max(len(part), 1))(*(part[:, 0] - r0).tolist())
                 count = (ctypes.c_int32 * max(len(part), 1))(*part[:, 1].tolist())
                 pieces.append((r0, r1 - r0, begin, count, len(part)))
-                self._grow_work(view.device, getattr(self._lib, self._abi[1] + "_seg"), r1 - r0, 1, len(part))
-        stream = _stream(view.device)
-        for r0, m, begin, count, n_seg in pieces:
-            rc = call(ctypes.byref(self.shape), ctypes.byref(self._w), view[r0:].data_ptr(), feature[r0:].data_ptr(), m, u[r0:].data_ptr(),
-                      self._work.data_ptr(), actions[r0:].data_ptr(), _ptr(None if policy is None else policy[r0:]),
-                      _ptr(None if value is None else value[r0:]), stream, begin, count, n_seg)
-            if rc != 0:
-                raise RuntimeError("%s failed (%d)" % (entry, rc))
+                self._grow_work(dev, getattr(self._lib, self._abi[1] + "_seg"), r1 - r0, 1, len(part))
+        return pieces
 
 
 class HipA2cPolicyF32(_A2cPolicy):
     """one acting step of an _ActorCritic in float32 -- the two input layers (k_a2c_trunk_f32), dense 512 and the two CommNet steps
-    (k_a2c_layer_f32, the column sums by k_a2c_colsum_part_f32 + k_a2c_colsum_f32), the policy and value heads, the softmax and the draw
+    (k_a2c_layer_f32, the column sums by k_a2c_colsum_part + k_a2c_colsum), the policy and value heads, the softmax and the draw
     (k_a2c_head_f32): magent_amd/csrc/policy_a2c_f32.hip.  The draw, the chunking and the CommNet rule: _A2cPolicy."""
     _abi, _struct = ("policy_a2c_f32_supported", "policy_a2c_f32_workspace_bytes", "f32"), _A2cWeights
 
@@ -602,8 +601,8 @@ class HipA2cPolicyF32(_A2cPolicy):
 
 class HipA2cPolicy(_A2cPolicy):
     """one acting step of an _ActorCritic with bf16 matrix operands -- the two input layers (k_a2c_trunk_bf16, from float32 views or from
-    the engine's bf16 cells), dense 512 and the two CommNet steps (k_a2c_layer_bf16, the column sums by k_a2c_colsum_part_bf16 +
-    k_a2c_colsum_bf16), the heads, the softmax and the draw (k_a2c_head_bf16): magent_amd/csrc/policy_a2c_bf16.hip.  Accumulation, biases,
+    the engine's bf16 cells), dense 512 and the two CommNet steps (k_a2c_layer_bf16, the column sums by k_a2c_colsum_part +
+    k_a2c_colsum), the heads, the softmax and the draw (k_a2c_head_bf16): magent_amd/csrc/policy_a2c_bf16.hip.  Accumulation, biases,
     relu / tanh, the column sums, the softmax and the draw are float32; the rounding points are listed in include/magent_policy.h.
 
     The draw, the chunking and the CommNet rule: _A2cPolicy.  `cells`: whether the shape has a cell entry (view_c <= 7 and 8 H W <= 4096)."""

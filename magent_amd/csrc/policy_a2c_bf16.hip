@@ -31,16 +31,15 @@
 //   [others | h] against [C_s | H_s]; others is formed from the stored row and the column sums -- in LDS -- as the operand is fed; the
 //   skip row and tanh in the epilogue).  Three register buffers of two k-steps (policy_bf16_dev.h: ring3).  Both GEMM kernels take
 //   their (tile group, agent group) from policy_bf16_dev.h: xcd_place, and their grid from xcd_grid.
-// k_a2c_colsum_part_bf16 + k_a2c_colsum_bf16 : the f32 path's column sums (policy_f32_dev.h: colsum_part, colsum_blocks) over the bf16
-//   rows, added in float32 -- partial sums over blocks of 256 agents in agent order, then the blocks in block order.  No atomics: the
-//   sums are a function of the call's inputs alone.
-// The segmented call (policy_a2c_infer_seg, policy_a2c_infer_bf16_seg): k_a2c_segmap_bf16, k_a2c_colsum_part_seg_bf16 +
-//   k_a2c_colsum_seg_bf16 as in policy_a2c_f32.hip (the same bodies), and k_a2c_layer_bf16<true, true>: the sum row, the divisor and
-//   `alone` per lane.  Its sums do not go through LDS (a workgroup may touch as many segments as it has agents): a lane loads the eight
-//   float32 sums of a k-step from its segment's row with the k-step's operands, through three register buffers of ONE k-step.
+// k_a2c_colsum_part<bf16_t> + k_a2c_colsum, and the segmented call's k_a2c_segmap, k_a2c_colsum_part_seg<bf16_t> + k_a2c_colsum_seg
+//   (policy_a2c_infer_seg, policy_a2c_infer_bf16_seg): the f32 path's kernels (policy_host.h) over the bf16 rows,
+//   added in float32.  k_a2c_layer_bf16<true, true>: the sum row, the divisor and `alone` per lane.  Its sums do not go through LDS (a
+//   workgroup may touch as many segments as it has agents): a lane loads the eight float32 sums of a k-step from its segment's row with
+//   the k-step's operands, through three register buffers of ONE k-step.
 // k_a2c_head_bf16 : [32 outputs] x [32 agents] per wave over K = 512 (policy_bf16_dev.h: head_gemm512_bf16, shared with
 //   k_drqn_head_bf16; the operand as stored), float32 biases, then policy_f32_dev.h: policy_epilogue, the f32 head's own softmax, clamp
-//   and draw.  The workspace layout is policy_host.h: a2c_layout, the f32 path's with 2-byte row elements.
+//   and draw.  The workspace layout (a2c_layout, the f32 path's with 2-byte row elements) and the driver of the launches (a2c_infer) are
+//   policy_host.h's; this file gives the driver the trait Bf16.
 //
 // Whole waves exit early (the head's stay for its barrier); lanes past n repeat the last agent (their own columns of the MFMA, never stored).
 // NaN contract: relu is IEEE maximum, tanhf keeps a NaN, the roundings keep a NaN; without CommNet a NaN or Inf in an
@@ -194,7 +193,7 @@ struct LayerArgs {
     const float *bias;        // [512] (dense)
     bf16_t *out;              // [n][512]
     int n, groups;
-    const int *row_seg;       // [n], seg_tab [n_seg][4]: the segmented call's maps (policy_f32_dev.h: seg_map); `sum` is then [n_seg][512]
+    const int *row_seg;       // [n], seg_tab [n_seg][4]: the segmented call's maps (policy_host.h: k_a2c_segmap); `sum` is then [n_seg][512]
     const int *seg_tab;
 };
 
@@ -301,23 +300,6 @@ __global__ void __launch_bounds__(GEMM_THREADS) k_a2c_layer_bf16(LayerArgs A) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------- column sums in a fixed order
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_bf16(const bf16_t *h, int n, float *part) {      // policy_f32_dev.h: colsum_part
-    magent_amd::f32::colsum_part(n, part, [&](size_t i) { return bf_lo(h[i]); });
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_bf16(const float *part, int n_blocks, float *sum) { magent_amd::f32::colsum_blocks(part, n_blocks, sum); }
-// the segmented call's: the maps (policy_f32_dev.h: seg_map), then the sums per segment (colsum_part_seg, colsum_blocks_seg)
-constexpr int SM_THREADS = 256;
-__global__ void __launch_bounds__(SM_THREADS) k_a2c_segmap_bf16(magent_amd::A2cSegTable t, int n, int *row_seg, int *seg_tab, int *blk_map) {
-    magent_amd::f32::seg_map(t, n, row_seg, seg_tab, blk_map);
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_seg_bf16(const bf16_t *h, const int *seg_tab, const int *blk_map, float *part) {
-    magent_amd::f32::colsum_part_seg(seg_tab, blk_map, part, [&](size_t i) { return bf_lo(h[i]); });
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_seg_bf16(const float *part, const int *seg_tab, float *sum) {
-    magent_amd::f32::colsum_blocks_seg(part, seg_tab, sum);
-}
-
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
 constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES;
 
@@ -346,74 +328,46 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_bf16(PHeadArgs A) {
     policy_epilogue(acc, g, A.n_action, s_p + (w * 32 + r32) * POLICY_ROW_PITCH, live, agent, A.u, A.actions, A.policy, A.value);
 }
 
-// ---------------------------------------------------------------------------------------------------- the workspace
-static magent_amd::A2cLayout layout(int n, bool comm) { return magent_amd::a2c_layout(n, comm, sizeof(bf16_t)); }      // policy_host.h
-static magent_amd::A2cSegLayout seg_layout(int n, bool comm, int n_seg) { return magent_amd::a2c_seg_layout(n, comm, sizeof(bf16_t), n_seg); }
-
+// ---------------------------------------------------------------------------------------------------- the launches
 static bool cells_supported(const PolicyDqnShape *s) { return s->view_c <= 7 && 8LL * s->view_h * s->view_w <= TR_KMAX; }
 
-static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view, bool cells, const float *feat, int n, const float *u,
-                     void *workspace, int *actions, float *policy, float *value, void *stream, const magent_amd::A2cSegTable *seg = nullptr) {
-    if (!s || !w || !policy_a2c_supported(s) || (cells && !cells_supported(s))) return 1;
-    const bool comm = w->use_comm != 0;
-    if (!(cells ? w->dense_view_cells : w->dense_view) || !w->dense_emb || !w->dense || !w->head || !w->dense_view_bias || !w->dense_emb_bias ||
-        !w->dense_bias || !w->head_bias) return 1;
-    if (comm && !(w->comm[0] && w->comm[1])) return 1;
-    if (n <= 0) return 0;
-    if (!view || !feat || !u || !actions || !workspace) return 1;
-    if ((uintptr_t)workspace & 15) return 1;                     // (rows are read as 16-byte units)
-    if (cells && ((uintptr_t)view & 15)) return 1;               // (a cell is one 16-byte load)
-    if (!comm) seg = nullptr;                                    // (every row is its own: the plain call)
-    hipStream_t st = (hipStream_t)stream;
-    magent_amd::StreamDevice on(st);
-    if (!on.ok) return 2;
-    const magent_amd::A2cLayout L = layout(n, comm);
-    const magent_amd::A2cSegLayout S = seg_layout(n, comm, seg ? seg->n_seg : 0);      // (x, h0 and h1 lie where L has them)
-    char *ws = (char *)workspace;
-    bf16_t *x = (bf16_t *)(ws + L.x), *h0 = (bf16_t *)(ws + L.h0);
-    const int groups = (n + 32 * GEMM_WAVES - 1) / (32 * GEMM_WAVES);
-    TrunkArgs T{};
-    T.view = view; T.feat = feat; T.wv = (const bf16x8 *)(cells ? w->dense_view_cells : w->dense_view); T.we = (const bf16x8 *)w->dense_emb;
-    T.bv = w->dense_view_bias; T.be = w->dense_emb_bias; T.n = n; T.groups = groups;
-    T.K = s->view_h * s->view_w * s->view_c; T.HW = s->view_h * s->view_w; T.KS = cells ? (T.HW + 1) / 2 : (T.K + 15) / 16;
-    T.F = s->feat; T.FS = (s->feat + 15) / 16; T.x = x;
-    if (cells) hipLaunchKernelGGL(k_a2c_trunk_bf16<true>, dim3(xcd_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
-    else hipLaunchKernelGGL(k_a2c_trunk_bf16<false>, dim3(xcd_grid(groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
-    const dim3 lgrid(xcd_grid(groups, LY_TG));
-    LayerArgs D{};
-    D.in = (const bf16x8 *)x; D.w = (const bf16x8 *)w->dense; D.bias = w->dense_bias; D.out = h0; D.n = n; D.groups = groups;
-    hipLaunchKernelGGL(k_a2c_layer_bf16<false>, lgrid, dim3(GEMM_THREADS), 0, st, D);
-    const bf16_t *h = h0;
-    if (comm) {
-        float *part = (float *)(ws + (seg ? S.part : L.part)), *sum = (float *)(ws + (seg ? S.sum : L.sum));
-        bf16_t *outs[2] = {x, (bf16_t *)(ws + L.h1)};            // (x is free once the dense layer has read it)
-        int *row_seg = (int *)(ws + S.row_seg), *seg_tab = (int *)(ws + S.seg_tab), *blk_map = (int *)(ws + S.blk_map);
-        const int seg_blocks = seg ? magent_amd::a2c_seg_blocks(*seg) : 0;
-        if (seg) hipLaunchKernelGGL(k_a2c_segmap_bf16, dim3(seg->n_seg > 0 ? seg->n_seg : 1), dim3(SM_THREADS), 0, st, *seg, n, row_seg, seg_tab, blk_map);
-        for (int step = 0; step < 2; step++) {
-            LayerArgs C{};
-            C.in = (const bf16x8 *)h; C.sum = sum; C.skip = h0; C.w = (const bf16x8 *)w->comm[step]; C.out = outs[step]; C.n = n; C.groups = groups;
-            if (seg) {
-                if (seg_blocks > 0) {                            // (no agent in any segment: no sum is read)
-                    hipLaunchKernelGGL(k_a2c_colsum_part_seg_bf16, dim3(seg_blocks), dim3(HID), 0, st, h, (const int *)seg_tab, (const int *)blk_map, part);
-                    hipLaunchKernelGGL(k_a2c_colsum_seg_bf16, dim3(seg->n_seg), dim3(HID), 0, st, (const float *)part, (const int *)seg_tab, sum);
-                }
-                C.row_seg = row_seg; C.seg_tab = seg_tab;
-                hipLaunchKernelGGL((k_a2c_layer_bf16<true, true>), lgrid, dim3(GEMM_THREADS), 0, st, C);
-            } else {
-                hipLaunchKernelGGL(k_a2c_colsum_part_bf16, dim3(L.n_blocks), dim3(HID), 0, st, h, n, part);
-                hipLaunchKernelGGL(k_a2c_colsum_bf16, dim3(1), dim3(HID), 0, st, (const float *)part, L.n_blocks, sum);
-                hipLaunchKernelGGL(k_a2c_layer_bf16<true>, lgrid, dim3(GEMM_THREADS), 0, st, C);
-            }
-            h = outs[step];
-        }
+// the bf16 trait of policy_host.h: a2c_infer, which owns the checks, the workspace and the order of the launches.  `cells`: the view
+// is the engine's cells (policy_a2c_infer_bf16*), not float32 views
+struct Bf16 {
+    typedef bf16_t Row;
+    typedef PolicyA2cWeights Weights;
+    bool cells;
+    bool supported(const PolicyDqnShape *s) const { return policy_a2c_supported(s) && (!cells || cells_supported(s)); }
+    const void *view_weights(const Weights *w) const { return cells ? w->dense_view_cells : w->dense_view; }
+    bool view_ok(const void *view) const { return !cells || !((uintptr_t)view & 15); }      // (a cell is one 16-byte load)
+    bool device_ready(int) const { return true; }
+    static int groups(int n) { return (n + 32 * GEMM_WAVES - 1) / (32 * GEMM_WAVES); }
+    void trunk(hipStream_t st, const PolicyDqnShape *s, const Weights *w, const void *view, const float *feat, int n, bf16_t *x) const {
+        TrunkArgs T{};
+        T.view = view; T.feat = feat; T.wv = (const bf16x8 *)view_weights(w); T.we = (const bf16x8 *)w->dense_emb;
+        T.bv = w->dense_view_bias; T.be = w->dense_emb_bias; T.n = n; T.groups = groups(n);
+        T.K = s->view_h * s->view_w * s->view_c; T.HW = s->view_h * s->view_w; T.KS = cells ? (T.HW + 1) / 2 : (T.K + 15) / 16;
+        T.F = s->feat; T.FS = (s->feat + 15) / 16; T.x = x;
+        if (cells) hipLaunchKernelGGL(k_a2c_trunk_bf16<true>, dim3(xcd_grid(T.groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
+        else hipLaunchKernelGGL(k_a2c_trunk_bf16<false>, dim3(xcd_grid(T.groups, TR_TG)), dim3(GEMM_THREADS), 0, st, T);
     }
-    PHeadArgs P{};
-    P.h = (const bf16x8 *)h; P.wh = (const bf16x8 *)w->head; P.bh = w->head_bias; P.u = u; P.n = n; P.n_action = s->n_action;
-    P.actions = actions; P.policy = policy; P.value = value;
-    hipLaunchKernelGGL(k_a2c_head_bf16, dim3((n + 32 * PH_WAVES - 1) / (32 * PH_WAVES)), dim3(PH_THREADS), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
+    void layer(hipStream_t st, magent_amd::A2cLayerKind kind, int n, const magent_amd::A2cLayerIo<bf16_t> &io) const {
+        LayerArgs A{};
+        A.in = (const bf16x8 *)io.in; A.sum = io.sum; A.skip = io.skip; A.w = (const bf16x8 *)io.w; A.bias = io.bias; A.out = io.out;
+        A.n = n; A.groups = groups(n); A.row_seg = io.row_seg; A.seg_tab = io.seg_tab;
+        const dim3 grid(xcd_grid(A.groups, LY_TG)), block(GEMM_THREADS);
+        if (kind == magent_amd::A2C_DENSE) hipLaunchKernelGGL(k_a2c_layer_bf16<false>, grid, block, 0, st, A);
+        else if (kind == magent_amd::A2C_COMM) hipLaunchKernelGGL(k_a2c_layer_bf16<true>, grid, block, 0, st, A);
+        else hipLaunchKernelGGL((k_a2c_layer_bf16<true, true>), grid, block, 0, st, A);
+    }
+    void head(hipStream_t st, const PolicyDqnShape *s, const Weights *w, const bf16_t *h, const float *u, int n, int *actions, float *policy,
+              float *value) const {
+        PHeadArgs P{};
+        P.h = (const bf16x8 *)h; P.wh = (const bf16x8 *)w->head; P.bh = w->head_bias; P.u = u; P.n = n; P.n_action = s->n_action;
+        P.actions = actions; P.policy = policy; P.value = value;
+        hipLaunchKernelGGL(k_a2c_head_bf16, dim3((n + 32 * PH_WAVES - 1) / (32 * PH_WAVES)), dim3(PH_THREADS), 0, st, P);
+    }
+};
 
 }  // namespace
 
@@ -425,42 +379,36 @@ int policy_a2c_supported(const PolicyDqnShape *s) {
     return views ? (cells_supported(s) ? 3 : 1) : 0;
 }
 
-int policy_a2c_workspace_bytes(const PolicyDqnShape *s, int n, int use_comm, size_t *bytes) {
-    (void)s;
-    *bytes = layout(n < 0 ? 0 : n, use_comm != 0).bytes;
+int policy_a2c_workspace_bytes(const PolicyDqnShape *, int n, int use_comm, size_t *bytes) {
+    *bytes = magent_amd::a2c_workspace_bytes(n, use_comm, sizeof(bf16_t), -1);
     return 0;
 }
 
 int policy_a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeights *w, const float *view, const float *feat, int n, const float *u,
                      void *workspace, int *actions, float *policy, float *value, void *stream) {
-    return a2c_infer(s, w, view, false, feat, n, u, workspace, actions, policy, value, stream);
+    return magent_amd::a2c_infer(Bf16{false}, s, w, view, feat, n, u, workspace, actions, policy, value, stream, {});
 }
 
 int policy_a2c_infer_bf16(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view_cells, const float *feat, int n, const float *u,
                           void *workspace, int *actions, float *policy, float *value, void *stream) {
-    return a2c_infer(s, w, view_cells, true, feat, n, u, workspace, actions, policy, value, stream);
+    return magent_amd::a2c_infer(Bf16{true}, s, w, view_cells, feat, n, u, workspace, actions, policy, value, stream, {});
 }
 
-int policy_a2c_workspace_bytes_seg(const PolicyDqnShape *s, int n, int use_comm, int n_seg, size_t *bytes) {
-    (void)s;
-    *bytes = seg_layout(n < 0 ? 0 : n, use_comm != 0, n_seg < 0 ? 0 : n_seg).bytes;
+int policy_a2c_workspace_bytes_seg(const PolicyDqnShape *, int n, int use_comm, int n_seg, size_t *bytes) {
+    *bytes = magent_amd::a2c_workspace_bytes(n, use_comm, sizeof(bf16_t), n_seg < 0 ? 0 : n_seg);
     return 0;
 }
 
 int policy_a2c_infer_seg(const PolicyDqnShape *s, const PolicyA2cWeights *w, const float *view, const float *feat, int n, const float *u,
                          void *workspace, int *actions, float *policy, float *value, void *stream, const int *seg_begin,
                          const int *seg_count, int n_seg) {
-    magent_amd::A2cSegTable t;
-    if (!magent_amd::a2c_seg_table(seg_begin, seg_count, n_seg, n, &t)) return 1;
-    return a2c_infer(s, w, view, false, feat, n, u, workspace, actions, policy, value, stream, &t);
+    return magent_amd::a2c_infer(Bf16{false}, s, w, view, feat, n, u, workspace, actions, policy, value, stream, {true, seg_begin, seg_count, n_seg});
 }
 
 int policy_a2c_infer_bf16_seg(const PolicyDqnShape *s, const PolicyA2cWeights *w, const void *view_cells, const float *feat, int n,
                               const float *u, void *workspace, int *actions, float *policy, float *value, void *stream,
                               const int *seg_begin, const int *seg_count, int n_seg) {
-    magent_amd::A2cSegTable t;
-    if (!magent_amd::a2c_seg_table(seg_begin, seg_count, n_seg, n, &t)) return 1;
-    return a2c_infer(s, w, view_cells, true, feat, n, u, workspace, actions, policy, value, stream, &t);
+    return magent_amd::a2c_infer(Bf16{true}, s, w, view_cells, feat, n, u, workspace, actions, policy, value, stream, {true, seg_begin, seg_count, n_seg});
 }
 
 }  // extern "C"

@@ -23,15 +23,11 @@
 //   registers).  A wave owns 32 agents x 4 output tiles (four accumulators: per group of 8 K-values one activation float4 and four weight
 //   float4 feed 16 MFMAs), operands of the next two groups load while the current two's 32 MFMAs run (policy_f32_dev.h: pingpong, the
 //   driver k_drqn_gru_f32 uses), from L2 / HBM.
-// k_a2c_colsum_part_f32 + k_a2c_colsum_f32 : the CommNet column sums without float atomics -- partial sums over blocks of 256 agents (block
-//   b: agents 256 b .. 256 b + 255 of the call, added in agent order), then the blocks added in block order.  The sums are a function of
-//   the call's inputs alone.  The bodies are policy_f32_dev.h: colsum_part / colsum_blocks, the bf16 path's too; the workspace layout is
-//   policy_host.h: a2c_layout, the bf16 path's too.
-// The segmented call (policy_a2c_infer_f32_seg): n packed rows and a table of segments (begin, count); the means run over
-//   the agent's own segment.  k_a2c_segmap_f32 spreads the table (its by-value argument) into the workspace (policy_f32_dev.h: seg_map),
-//   k_a2c_colsum_part_seg_f32 + k_a2c_colsum_seg_f32 take every segment's sums over blocks of 256 agents counted from the segment's own
-//   first row -- the plain call's partition and order on that segment alone, hence its bits --, and k_a2c_layer_f32<true, true> takes the
-//   sum row, the divisor and `alone` per lane from the lane's agent's segment (a row in no segment: alone).  The other kernels are per row.
+// k_a2c_colsum_part<float> + k_a2c_colsum : the CommNet column sums without float atomics, in a fixed order; the segmented call
+//   (policy_a2c_infer_f32_seg) has k_a2c_segmap and k_a2c_colsum_part_seg<float> + k_a2c_colsum_seg in their place, and
+//   k_a2c_layer_f32<true, true> takes the sum row, the divisor and `alone` per lane from the lane's agent's segment (a row in no
+//   segment: alone).  Those kernels, the workspace layout (a2c_layout) and the driver of the launches (a2c_infer) are
+//   policy_host.h's, the bf16 path's too; this file gives the driver the trait F32.
 // k_a2c_head_f32 : [32 outputs] x [32 agents] per wave over K = 512 (head_gemm512; outputs 0..A-1 the policy's, output A the value's), softmax with the
 //   row maximum subtracted, clamp, and the draw by the lane that holds the agent's action 0 (the row goes through LDS: a lane pair holds it).
 //
@@ -107,7 +103,7 @@ struct LayerArgs {
     const float *bias;        // [512] (dense)
     float *out;               // [n][512]
     int n;
-    const int *row_seg;       // [n], seg_tab [n_seg][4]: the segmented call's maps (policy_f32_dev.h: seg_map); `sum` is then [n_seg][512]
+    const int *row_seg;       // [n], seg_tab [n_seg][4]: the segmented call's maps (policy_host.h: k_a2c_segmap); `sum` is then [n_seg][512]
     const int *seg_tab;
 };
 
@@ -177,21 +173,6 @@ __global__ void __launch_bounds__(LY_THREADS) k_a2c_layer_f32(LayerArgs A) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------- column sums in a fixed order
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_f32(const float *h, int n, float *part) {      // policy_f32_dev.h: colsum_part
-    colsum_part(n, part, [&](size_t i) { return h[i]; });
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_f32(const float *part, int n_blocks, float *sum) { colsum_blocks(part, n_blocks, sum); }
-// the segmented call's: the maps (policy_f32_dev.h: seg_map), then the sums per segment (colsum_part_seg, colsum_blocks_seg)
-constexpr int SM_THREADS = 256;
-__global__ void __launch_bounds__(SM_THREADS) k_a2c_segmap_f32(magent_amd::A2cSegTable t, int n, int *row_seg, int *seg_tab, int *blk_map) {
-    seg_map(t, n, row_seg, seg_tab, blk_map);
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_part_seg_f32(const float *h, const int *seg_tab, const int *blk_map, float *part) {
-    colsum_part_seg(seg_tab, blk_map, part, [&](size_t i) { return h[i]; });
-}
-__global__ void __launch_bounds__(HID) k_a2c_colsum_seg_f32(const float *part, const int *seg_tab, float *sum) { colsum_blocks_seg(part, seg_tab, sum); }
-
 // ---------------------------------------------------------------------------------------------------- the heads and the draw
 constexpr int PH_WAVES = 4, PH_THREADS = 64 * PH_WAVES, PH_PITCH = POLICY_ROW_PITCH;
 
@@ -220,68 +201,42 @@ __global__ void __launch_bounds__(PH_THREADS) k_a2c_head_f32(PHeadArgs A) {
     policy_epilogue(acc, g, A.n_action, s_p + (w * 32 + r32) * PH_PITCH, live, agent, A.u, A.actions, A.policy, A.value);
 }
 
-// ---------------------------------------------------------------------------------------------------- the workspace
-static magent_amd::A2cLayout layout(int n, bool comm) { return magent_amd::a2c_layout(n, comm, sizeof(float)); }      // policy_host.h
-static magent_amd::A2cSegLayout seg_layout(int n, bool comm, int n_seg) { return magent_amd::a2c_seg_layout(n, comm, sizeof(float), n_seg); }
-
-// policy_a2c_infer_f32 (seg == nullptr) and policy_a2c_infer_f32_seg (the validated table; looked at with CommNet only)
-static int a2c_infer(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, const float *view, const float *feat, int n, const float *u,
-                     void *workspace, int *actions, float *policy, float *value, void *stream, const magent_amd::A2cSegTable *seg) {
-    if (!s || !w || !policy_a2c_f32_supported(s)) return 1;
-    const bool comm = w->use_comm != 0;
-    if (!w->dense_view || !w->dense_emb || !w->dense || !w->head || !w->dense_view_bias || !w->dense_emb_bias || !w->dense_bias || !w->head_bias) return 1;
-    if (comm && !(w->comm[0] && w->comm[1])) return 1;
-    if (n <= 0) return 0;
-    if (!view || !feat || !u || !actions || !workspace) return 1;
-    if ((uintptr_t)workspace & 15) return 1;                     // (rows are read and written as float4)
-    if (!comm) seg = nullptr;                                    // (every row is its own: the plain call)
-    hipStream_t st = (hipStream_t)stream;
-    magent_amd::StreamDevice on(st);
-    static magent_amd::LdsAllowance lds_ok;
-    if (!on.ok || !lds_ok.grant(on.dev, {{reinterpret_cast<const void *>(k_a2c_trunk_f32), (int)TR_LDS}})) return 2;
-    const magent_amd::A2cLayout L = layout(n, comm);
-    const magent_amd::A2cSegLayout S = seg_layout(n, comm, seg ? seg->n_seg : 0);      // (x, h0 and h1 lie where L has them)
-    char *ws = (char *)workspace;
-    float *x = (float *)(ws + L.x), *h0 = (float *)(ws + L.h0);
-    TrunkArgs T{};
-    T.view = view; T.feat = feat; T.wv = (const f32x4 *)w->dense_view; T.we = (const f32x4 *)w->dense_emb; T.bv = w->dense_view_bias; T.be = w->dense_emb_bias;
-    T.n = n; T.K = s->view_h * s->view_w * s->view_c; T.KG = (T.K + 7) / 8; T.F = s->feat; T.FK = (s->feat + 7) / 8 * 8; T.x = x;
-    hipLaunchKernelGGL(k_a2c_trunk_f32, dim3((n + TR_M - 1) / TR_M), dim3(TR_THREADS), TR_LDS, st, T);
-    const dim3 lgrid((n + 32 * LY_WAVES - 1) / (32 * LY_WAVES), HID / 32 / LY_TILES);
-    LayerArgs D{};
-    D.in = x; D.w = (const f32x4 *)w->dense; D.bias = w->dense_bias; D.out = h0; D.n = n;
-    hipLaunchKernelGGL(k_a2c_layer_f32<false>, lgrid, dim3(LY_THREADS), 0, st, D);
-    const float *h = h0;
-    if (comm) {
-        float *part = (float *)(ws + (seg ? S.part : L.part)), *sum = (float *)(ws + (seg ? S.sum : L.sum));
-        float *outs[2] = {x, (float *)(ws + L.h1)};              // (x is free once the dense layer has read it)
-        int *row_seg = (int *)(ws + S.row_seg), *seg_tab = (int *)(ws + S.seg_tab), *blk_map = (int *)(ws + S.blk_map);
-        const int seg_blocks = seg ? magent_amd::a2c_seg_blocks(*seg) : 0;
-        if (seg) hipLaunchKernelGGL(k_a2c_segmap_f32, dim3(seg->n_seg > 0 ? seg->n_seg : 1), dim3(SM_THREADS), 0, st, *seg, n, row_seg, seg_tab, blk_map);
-        for (int step = 0; step < 2; step++) {
-            LayerArgs C{};
-            C.in = h; C.sum = sum; C.skip = h0; C.w = (const f32x4 *)w->comm[step]; C.out = outs[step]; C.n = n;
-            if (seg) {
-                if (seg_blocks > 0) {                            // (no agent in any segment: no sum is read)
-                    hipLaunchKernelGGL(k_a2c_colsum_part_seg_f32, dim3(seg_blocks), dim3(HID), 0, st, h, (const int *)seg_tab, (const int *)blk_map, part);
-                    hipLaunchKernelGGL(k_a2c_colsum_seg_f32, dim3(seg->n_seg), dim3(HID), 0, st, (const float *)part, (const int *)seg_tab, sum);
-                }
-                C.row_seg = row_seg; C.seg_tab = seg_tab;
-                hipLaunchKernelGGL((k_a2c_layer_f32<true, true>), lgrid, dim3(LY_THREADS), 0, st, C);
-            } else {
-                hipLaunchKernelGGL(k_a2c_colsum_part_f32, dim3(L.n_blocks), dim3(HID), 0, st, h, n, part);
-                hipLaunchKernelGGL(k_a2c_colsum_f32, dim3(1), dim3(HID), 0, st, (const float *)part, L.n_blocks, sum);
-                hipLaunchKernelGGL(k_a2c_layer_f32<true>, lgrid, dim3(LY_THREADS), 0, st, C);
-            }
-            h = outs[step];
-        }
+// ---------------------------------------------------------------------------------------------------- the launches
+// the float32 trait of policy_host.h: a2c_infer, which owns the checks, the workspace and the order of the launches
+struct F32 {
+    typedef float Row;
+    typedef PolicyA2cWeightsF32 Weights;
+    bool supported(const PolicyDqnShape *s) const { return policy_a2c_f32_supported(s) != 0; }
+    const void *view_weights(const Weights *w) const { return w->dense_view; }
+    bool view_ok(const void *) const { return true; }            // (view rows are read by 4-byte loads)
+    bool device_ready(int dev) const {
+        static magent_amd::LdsAllowance lds_ok;
+        return lds_ok.grant(dev, {{reinterpret_cast<const void *>(k_a2c_trunk_f32), (int)TR_LDS}});
     }
-    PHeadArgs P{};
-    P.h = h; P.wh = (const f32x4 *)w->head; P.bh = w->head_bias; P.u = u; P.n = n; P.n_action = s->n_action;
-    P.actions = actions; P.policy = policy; P.value = value;
-    hipLaunchKernelGGL(k_a2c_head_f32, dim3((n + 32 * PH_WAVES - 1) / (32 * PH_WAVES)), dim3(PH_THREADS), 0, st, P);
-    return hipGetLastError() == hipSuccess ? 0 : 3;
-}
+    void trunk(hipStream_t st, const PolicyDqnShape *s, const Weights *w, const void *view, const float *feat, int n, float *x) const {
+        TrunkArgs T{};
+        T.view = (const float *)view; T.feat = feat; T.wv = (const f32x4 *)w->dense_view; T.we = (const f32x4 *)w->dense_emb;
+        T.bv = w->dense_view_bias; T.be = w->dense_emb_bias;
+        T.n = n; T.K = s->view_h * s->view_w * s->view_c; T.KG = (T.K + 7) / 8; T.F = s->feat; T.FK = (s->feat + 7) / 8 * 8; T.x = x;
+        hipLaunchKernelGGL(k_a2c_trunk_f32, dim3((n + TR_M - 1) / TR_M), dim3(TR_THREADS), TR_LDS, st, T);
+    }
+    void layer(hipStream_t st, magent_amd::A2cLayerKind kind, int n, const magent_amd::A2cLayerIo<float> &io) const {
+        LayerArgs A{};
+        A.in = io.in; A.sum = io.sum; A.skip = io.skip; A.w = (const f32x4 *)io.w; A.bias = io.bias; A.out = io.out; A.n = n;
+        A.row_seg = io.row_seg; A.seg_tab = io.seg_tab;
+        const dim3 grid((n + 32 * LY_WAVES - 1) / (32 * LY_WAVES), HID / 32 / LY_TILES), block(LY_THREADS);
+        if (kind == magent_amd::A2C_DENSE) hipLaunchKernelGGL(k_a2c_layer_f32<false>, grid, block, 0, st, A);
+        else if (kind == magent_amd::A2C_COMM) hipLaunchKernelGGL(k_a2c_layer_f32<true>, grid, block, 0, st, A);
+        else hipLaunchKernelGGL((k_a2c_layer_f32<true, true>), grid, block, 0, st, A);
+    }
+    void head(hipStream_t st, const PolicyDqnShape *s, const Weights *w, const float *h, const float *u, int n, int *actions, float *policy,
+              float *value) const {
+        PHeadArgs P{};
+        P.h = h; P.wh = (const f32x4 *)w->head; P.bh = w->head_bias; P.u = u; P.n = n; P.n_action = s->n_action;
+        P.actions = actions; P.policy = policy; P.value = value;
+        hipLaunchKernelGGL(k_a2c_head_f32, dim3((n + 32 * PH_WAVES - 1) / (32 * PH_WAVES)), dim3(PH_THREADS), 0, st, P);
+    }
+};
 
 }  // namespace
 
@@ -292,29 +247,25 @@ int policy_a2c_f32_supported(const PolicyDqnShape *s) {
            s->feat <= TR_FMAX && s->n_action >= 1 && s->n_action <= 31;
 }
 
-int policy_a2c_f32_workspace_bytes(const PolicyDqnShape *s, int n, int use_comm, size_t *bytes) {
-    (void)s;
-    *bytes = layout(n < 0 ? 0 : n, use_comm != 0).bytes;
+int policy_a2c_f32_workspace_bytes(const PolicyDqnShape *, int n, int use_comm, size_t *bytes) {
+    *bytes = magent_amd::a2c_workspace_bytes(n, use_comm, sizeof(float), -1);
     return 0;
 }
 
 int policy_a2c_infer_f32(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, const float *view, const float *feat, int n, const float *u,
                          void *workspace, int *actions, float *policy, float *value, void *stream) {
-    return a2c_infer(s, w, view, feat, n, u, workspace, actions, policy, value, stream, nullptr);
+    return magent_amd::a2c_infer(F32{}, s, w, view, feat, n, u, workspace, actions, policy, value, stream, {});
 }
 
-int policy_a2c_f32_workspace_bytes_seg(const PolicyDqnShape *s, int n, int use_comm, int n_seg, size_t *bytes) {
-    (void)s;
-    *bytes = seg_layout(n < 0 ? 0 : n, use_comm != 0, n_seg < 0 ? 0 : n_seg).bytes;
+int policy_a2c_f32_workspace_bytes_seg(const PolicyDqnShape *, int n, int use_comm, int n_seg, size_t *bytes) {
+    *bytes = magent_amd::a2c_workspace_bytes(n, use_comm, sizeof(float), n_seg < 0 ? 0 : n_seg);
     return 0;
 }
 
 int policy_a2c_infer_f32_seg(const PolicyDqnShape *s, const PolicyA2cWeightsF32 *w, const float *view, const float *feat, int n, const float *u,
                              void *workspace, int *actions, float *policy, float *value, void *stream, const int *seg_begin,
                              const int *seg_count, int n_seg) {
-    magent_amd::A2cSegTable t;
-    if (!magent_amd::a2c_seg_table(seg_begin, seg_count, n_seg, n, &t)) return 1;
-    return a2c_infer(s, w, view, feat, n, u, workspace, actions, policy, value, stream, &t);
+    return magent_amd::a2c_infer(F32{}, s, w, view, feat, n, u, workspace, actions, policy, value, stream, {true, seg_begin, seg_count, n_seg});
 }
 
 }  // extern "C"

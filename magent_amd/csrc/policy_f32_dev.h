@@ -12,8 +12,8 @@
 //   policy_epilogue                                  softmax, clamp, the stores and the inverse-CDF draw (k_a2c_head_f32, k_a2c_head_bf16)
 //   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, head_gemm512_bf16)
 //   state_row                                        the id table's look-up (k_drqn_gru_f32, k_drqn_gru_bf16)
-//   colsum_part, colsum_blocks                       the CommNet column sums' bodies (the four k_a2c_colsum* kernels)
-//   seg_map, colsum_part_seg, colsum_blocks_seg, seg_of_row   the segmented A2C call's maps and sums (both k_a2c_segmap_*, the four *_seg_* kernels)
+//   colsum_rows, colsum_blocks                       the CommNet column sums' bodies (policy_host.h: the k_a2c_colsum* kernels)
+//   seg_map, colsum_part_seg, colsum_blocks_seg, seg_of_row   the segmented A2C call's maps and sums (k_a2c_segmap, the *_seg kernels, the layers)
 // The bf16 files take their float32 side from here too (policy_bf16_dev.h includes this header): policy.hip the vector types, out_of
 // and q_before; policy_drqn_bf16.hip out_of, sigmoid, q_epilogue and state_row (its gates, blend and epilogue are float32);
 // policy_a2c_bf16.hip out_of, relu, policy_epilogue and the column sums.
@@ -22,9 +22,14 @@
 #include <stddef.h>
 
 #include "../../include/magent_policy.h"
-#include "policy_host.h"
 
 namespace magent_amd {
+
+// The A2C: rows of A2C_HID units; column sums over blocks of A2C_CS_BLOCK agents.  The segmented call's table (policy_a2c_infer*_seg: n
+// packed rows and segments (begin, count)) travels to the device by value, as the argument of k_a2c_segmap (policy_host.h).
+constexpr int A2C_HID = 512, A2C_CS_BLOCK = 256, A2C_MAX_SEGMENTS = POLICY_A2C_MAX_SEGMENTS;
+struct A2cSegTable { int n_seg; int begin[A2C_MAX_SEGMENTS]; int count[A2C_MAX_SEGMENTS]; };
+
 namespace f32 {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -294,15 +299,18 @@ __device__ __forceinline__ const float *state_row(int id, const int *prev_ids, c
 }
 
 // ---------------------------------------------------------------------------------------------------- column sums in a fixed order
-// Workgroups of A2C_HID threads, thread c = column c.  colsum_part: block b adds agents A2C_CS_BLOCK b .. + A2C_CS_BLOCK - 1 of the
-// call in agent order, at(i) = element i of the rows [n][A2C_HID] as float32; colsum_blocks: one workgroup adds the blocks in block order.
-template <class At>
-__device__ __forceinline__ void colsum_part(int n, float *part, const At &at) {
-    const int c = threadIdx.x, beg = blockIdx.x * A2C_CS_BLOCK, end = min(beg + A2C_CS_BLOCK, n);
+// Workgroups of A2C_HID threads, thread c = column c.  colsum_rows: rows beg .. end - 1 of h [n][A2C_HID] (an element as float32: row_f32
+// of its type) added in row order into row `part_row` of part -- the plain call's block b: agents A2C_CS_BLOCK b .. + A2C_CS_BLOCK - 1,
+// a segmented call's: see below; colsum_blocks: one workgroup adds the blocks in block order.
+__device__ __forceinline__ float row_f32(float v) { return v; }
+__device__ __forceinline__ float row_f32(unsigned short v) { return __uint_as_float((unsigned)v << 16); }      // a stored bf16 value
+template <class Row>
+__device__ __forceinline__ void colsum_rows(const Row *h, int beg, int end, float *part, int part_row) {
+    const int c = threadIdx.x;
     float s = 0.0f;
 #pragma unroll 16
-    for (int a = beg; a < end; a++) s += at((size_t)a * A2C_HID + c);
-    part[(size_t)blockIdx.x * A2C_HID + c] = s;
+    for (int a = beg; a < end; a++) s += row_f32(h[(size_t)a * A2C_HID + c]);
+    part[(size_t)part_row * A2C_HID + c] = s;
 }
 __device__ __forceinline__ void colsum_blocks(const float *part, int n_blocks, float *sum) {
     const int c = threadIdx.x;
@@ -312,9 +320,9 @@ __device__ __forceinline__ void colsum_blocks(const float *part, int n_blocks, f
     sum[c] = s;
 }
 
-// The same sums per segment of a segmented call (policy_host.h: A2cSegTable, a2c_seg_layout).  Segment s is cut into blocks of
+// The same sums per segment of a segmented call (A2cSegTable above; policy_host.h: a2c_layout).  Segment s is cut into blocks of
 // A2C_CS_BLOCK agents counted from ITS first row; a block is added in agent order, a segment's blocks in block order: the partition and
-// the order of colsum_part / colsum_blocks on that segment alone, so the sums have that call's bits.
+// the order of the plain call's blocks on that segment alone, so the sums have that call's bits.
 // seg_map: workgroup s (of max(n_seg, 1), any size) writes segment s's entry of seg_tab, its blocks' entries of blk_map, and row_seg of
 // the segment's rows and of the rows between it and the next segment (-1; workgroup 0 also the rows in front of the first segment).
 __device__ __forceinline__ void seg_map(const A2cSegTable &t, int n, int *row_seg, int *seg_tab, int *blk_map) {
@@ -334,14 +342,10 @@ __device__ __forceinline__ void seg_map(const A2cSegTable &t, int n, int *row_se
     for (int r = (s == 0 ? 0 : beg) + tid; r < next; r += step) row_seg[r] = (r >= beg && r < beg + cnt) ? s : -1;
 }
 // workgroup b of sum over s of ceil(count_s / A2C_CS_BLOCK): the partial row of block blk_map[b]
-template <class At>
-__device__ __forceinline__ void colsum_part_seg(const int *seg_tab, const int *blk_map, float *part, const At &at) {
-    const int c = threadIdx.x, s = blk_map[2 * blockIdx.x], k = blk_map[2 * blockIdx.x + 1];
-    const int beg = seg_tab[4 * s] + k * A2C_CS_BLOCK, end = min(beg + A2C_CS_BLOCK, seg_tab[4 * s] + seg_tab[4 * s + 1]);
-    float sum = 0.0f;
-#pragma unroll 16
-    for (int a = beg; a < end; a++) sum += at((size_t)a * A2C_HID + c);
-    part[(size_t)blockIdx.x * A2C_HID + c] = sum;
+template <class Row>
+__device__ __forceinline__ void colsum_part_seg(const Row *h, const int *seg_tab, const int *blk_map, float *part) {
+    const int s = blk_map[2 * blockIdx.x], beg = seg_tab[4 * s] + blk_map[2 * blockIdx.x + 1] * A2C_CS_BLOCK;
+    colsum_rows(h, beg, min(beg + A2C_CS_BLOCK, seg_tab[4 * s] + seg_tab[4 * s + 1]), part, blockIdx.x);
 }
 // workgroup s: segment s's blocks in block order -> sum[s][A2C_HID] (an empty segment: zeros, never read)
 __device__ __forceinline__ void colsum_blocks_seg(const float *part, const int *seg_tab, float *sum) {

@@ -1,7 +1,7 @@
-"""Development helper: the bits of the policy kernels.  A fixed, seeded list of cases goes through all nine inference entries of
-include/magent_policy.h, called through the C-ABI as they are (the policy classes of hip_policy.py only pack the weights), and every
-output array -- actions, Q, p, value, new states --, every packed weight tensor and the five *_act_bytes / *_workspace_bytes sizes are
-written to an .npz as raw integer words.  Two such files of two builds (a commit and its parent; the emulated build and itself after a
+"""Development helper: the bits of the policy kernels.  A fixed, seeded list of cases goes through all twelve inference entries of
+include/magent_policy.h -- the nine plain ones and the three segmented A2C ones --, called through the C-ABI as they are (the policy
+classes of hip_policy.py only pack the weights), and every output array -- actions, Q, p, value, new states --, every packed weight
+tensor and the seven *_act_bytes / *_workspace_bytes / *_workspace_bytes_seg sizes are written to an .npz as raw integer words.  Two such files of two builds (a commit and its parent; the emulated build and itself after a
 refactor) must agree word for word: the kernels use no atomics, so their results are a function of the call's inputs alone.
 
     python tools/policy_bits.py LIB emu|cuda OUT.npz       LIB: a library with all of the entries -- the product library, or the emulated
@@ -12,7 +12,9 @@ The cases are the smallest at which each shared block can still go wrong: n = 1,
 256) and 2305 (10 agent groups: the XCD placement wraps past its first round of 8, the column sums take 10 blocks); for the DQN / DRQN
 both view classes (13 x 13: the F13 kernels) with dueling on and off and every DRQN case called twice -- an empty table, then one that
 holds duplicated ids, ids absent from the call and ids new to it; for the A2C an odd H W (the cell path's zero half k-step), rows that
-are only 4-byte aligned, a shape without a cell entry, 1 and 64 features, 1, 16 and 31 actions, CommNet on and off and alone (n = 1)."""
+are only 4-byte aligned, a shape without a cell entry, 1 and 64 features, 1, 16 and 31 actions, CommNet on and off and alone (n = 1); for the segmented A2C entries no segment at all over 33
+rows, the table of tests/test_a2c_segments.py LAYOUTS["a"] (an agent alone, an empty segment, a segment across a 32-agent tile, one
+whose sum blocks start off a multiple of 256), 256 one-row segments (the cap), and one table on a network without CommNet (ignored)."""
 import ctypes
 import os
 import sys
@@ -28,6 +30,9 @@ DRQN_CASES = [((9, 9, 5), 20, 5, False, 1), ((13, 13, 7), 34, 21, True, 33), ((1
 # (view space, features, actions, CommNet, n): A2C
 A2C_CASES = [((5, 5, 5), 1, 1, True, 1), ((13, 13, 7), 64, 16, False, 33), ((3, 3, 9), 64, 1, True, 257), ((13, 13, 7), 1, 31, True, 257),
              ((3, 3, 9), 1, 16, False, 2305), ((5, 5, 5), 64, 31, True, 2305)]
+# (view space, features, actions, CommNet, n, [(begin, count)]): the segmented A2C entries
+A2C_SEG_CASES = [((5, 5, 5), 1, 16, True, 33, []), ((5, 5, 3), 7, 9, True, 322, [(4, 1), (8, 0), (8, 33), (52, 257), (312, 2)]),
+                 ((3, 3, 9), 64, 31, True, 256, [(r, 1) for r in range(256)]), ((13, 13, 7), 34, 21, False, 33, [(1, 8), (12, 20)])]
 
 
 def words(t):
@@ -138,19 +143,27 @@ def run(lib, dev, out):
                     srt, perm = torch.sort(ids, stable=True)
                     table = (srt, perm.to(torch.int32), states, n)
 
-    for k, (vs, feat, A, comm, n) in enumerate(A2C_CASES):
-        torch.manual_seed(600 + k)
+    def a2c(tag, seed, vs, feat, A, comm, n, suffix="", table=()):
+        """every A2C entry (+ suffix) on one seeded network and n rows; table: a segmented entry's begin, count, n_seg"""
+        torch.manual_seed(seed)
         net = scaled(_ActorCritic(vs, (feat,), A, comm)).to(dev)
-        view, cells, featv, u = inputs(vs, feat, n, 700 + k, dev)
+        view, cells, featv, u = inputs(vs, feat, n, seed + 100, dev)
         for cls, pairs, bytes_fn in ((hp.HipA2cPolicy, [("policy_a2c_infer", view), ("policy_a2c_infer_bf16", cells)], "policy_a2c_workspace_bytes"),
                                      (hp.HipA2cPolicyF32, [("policy_a2c_infer_f32", view)], "policy_a2c_f32_workspace_bytes")):
-            pol = packed(cls(net, vs, (feat,), A, dev), "a2c%d/%s" % (k, cls.__name__))
-            work = size(bytes_fn, pol.shape, n, int(comm))
+            pol = packed(cls(net, vs, (feat,), A, dev), "%s/%s" % (tag, cls.__name__))
+            work = size(bytes_fn + suffix, pol.shape, n, int(comm), *table[2:])
             for entry, v in entries(pol, pairs, getattr(pol, "cells", False)):
                 actions, p, value = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros((n, A), device=dev), torch.zeros(n, device=dev)
-                check(getattr(lib, entry)(ref(pol.shape), ref(pol._w), ptr(v), ptr(featv), n, ptr(u), ptr(work), ptr(actions), ptr(p), ptr(value), None), entry)
-                tag = "%s/a2c%d" % (entry, k)
-                out[tag + "/actions"], out[tag + "/p"], out[tag + "/value"] = words(actions), words(p), words(value)
+                check(getattr(lib, entry + suffix)(ref(pol.shape), ref(pol._w), ptr(v), ptr(featv), n, ptr(u), ptr(work), ptr(actions), ptr(p),
+                                                   ptr(value), None, *table), entry + suffix)
+                out["%s%s/%s/actions" % (entry, suffix, tag)], out["%s%s/%s/p" % (entry, suffix, tag)] = words(actions), words(p)
+                out["%s%s/%s/value" % (entry, suffix, tag)] = words(value)
+
+    for k, (vs, feat, A, comm, n) in enumerate(A2C_CASES):
+        a2c("a2c%d" % k, 600 + k, vs, feat, A, comm, n)
+    for k, (vs, feat, A, comm, n, seg) in enumerate(A2C_SEG_CASES):
+        ints = lambda v: (ctypes.c_int32 * max(len(v), 1))(*v)
+        a2c("a2cseg%d" % k, 800 + k, vs, feat, A, comm, n, "_seg", (ints([b for b, _ in seg]), ints([c for _, c in seg]), len(seg)))
 
 
 def compare(a, b):
