@@ -164,6 +164,36 @@ int policy_drqn_infer_bf16(const PolicyDqnShape *shape, const PolicyDrqnWeights 
                            const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
                            void *workspace, int *actions, float *q, void *stream);
 
+/* ---- the segmented DRQN step: one call over the packed rows of many worlds (EnvBatch.packed_offsets), every world with its own id
+ * namespace.  The state table is keyed by (segment, id): it holds int64 keys (segment << 32) | uint32(id), sorted ascending (stably),
+ * in place of the plain entries' sorted ids.  Segment s of a call is world s; the plain entries' table is segment 0's.  Two steps:
+ *
+ * 1. policy_drqn_lookup_seg_f32 / policy_drqn_lookup_seg (one kernel, exported by either file family) -- ONE small launch over all n rows:
+ *      ids int[n]; the table seg_begin / seg_count / n_seg (HOST arrays) in policy_a2c_infer_f32_seg's format, with its validation and its
+ *      cap POLICY_A2C_MAX_SEGMENTS (it travels by value in the kernel's arguments); seg_first: the number of table segment 0 among the
+ *      call's segments (a call of more segments than the cap makes several look-ups over row ranges; 0 <= seg_first < 2^31 - 257);
+ *      prev_sorted_keys int64[count], rows int[count]: the previous call's table (count == 0: empty).
+ *    Writes from_row int[n]: for a row in a segment the row of the previous `states` that the LAST entry of prev_sorted_keys equal to its
+ *    key names (the plain entries' duplicate rule), -1 if there is none; -1 for a row in no segment.  Writes keys int64[n]: the row's key
+ *    in THIS call's table; a row in no segment gets 0x7FFFFFFFFFFFFFFF, which no look-up produces and which sorts to the end: pad and
+ *    stale rows stay in the table, nobody finds them, and no host synchronisation is needed to drop them.
+ *    Returns 0; 1 for a refused table or argument -- nothing is written --, 2 / 3 as the entries above.
+ * 2. policy_drqn_infer_f32_rows / policy_drqn_infer_rows / policy_drqn_infer_bf16_rows -- the plain entries with (ids, prev_sorted_ids,
+ *    rows, states, count) replaced by (from_row, states): agent i starts from row from_row[i] of `states`, or from zeros if from_row[i] < 0;
+ *    states == NULL is the empty table (gru_bias0, from_row is not read but must be given).  Rows are independent: any row range of the
+ *    call can go to a call of its own (from_row + beg).  Trunk, head, alignment rule (states, new_states, workspace: 16 bytes), return
+ *    codes and "a refused call has written nothing" are the plain entries'; the GRU kernels are the plain entries' own. */
+int policy_drqn_lookup_seg_f32(const int *ids, int n, const int *seg_begin, const int *seg_count, int n_seg, int seg_first,
+                               const long long *prev_sorted_keys, const int *rows, int count, int *from_row, long long *keys, void *stream);
+int policy_drqn_lookup_seg(const int *ids, int n, const int *seg_begin, const int *seg_count, int n_seg, int seg_first,
+                           const long long *prev_sorted_keys, const int *rows, int count, int *from_row, long long *keys, void *stream);
+int policy_drqn_infer_f32_rows(const PolicyDqnShape *shape, const PolicyDrqnWeightsF32 *weights, const float *view, const float *feature, int n,
+                               const int *from_row, const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream);
+int policy_drqn_infer_rows(const PolicyDqnShape *shape, const PolicyDrqnWeights *weights, const float *view, const float *feature, int n,
+                           const int *from_row, const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream);
+int policy_drqn_infer_bf16_rows(const PolicyDqnShape *shape, const PolicyDrqnWeights *weights, const void *view_cells, const float *feature, int n,
+                                const int *from_row, const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream);
+
 /* ---- one acting step of the advantage actor-critic (magent_amd/builtin/torch_model/a2c.py: _ActorCritic.forward, then the action draw)
  * in float32 -- magent_amd/csrc/policy_a2c_f32.hip.  No convolution: the flattened view (K = view_h * view_w * view_c values, in the
  * order env_get_observation_device writes them) feeds a dense layer.  Weights in f32 fragment order, biases in natural order:

@@ -164,6 +164,14 @@ int env_cycle_many_cells(EnvHandle *games, int n_env, int n_group, void **view, 
 int env_cycle_pool_stats(long long out[4]);
 /* out[e * n_group + g] = number of agents of group g in environment e (env_get_info "num" for a whole batch; host only) */
 int env_num_many(EnvHandle *games, int n_env, int n_group, int *out);
+/* env_get_info_device(e, g, "id", out[e * n_group + g]) for a whole batch in one launch: out[e * n_group + g] is a device pointer to
+ * int32[n of that group]; a NULL entry skips that group, and so does an empty group.  `name` is "id" only (anything else is FATAL).
+ * The (source, destination, n) items travel by value in the kernel's arguments, 192 to a launch (a larger batch takes several); no
+ * allocation, no copy, no host wait.  Unlike the calls above, the work is enqueued on `stream`, the CALLER's hipStream_t (NULL: the null
+ * stream): a caller that orders its stream behind the engine's (env_streams_many) reads the ids where it reads the observations.
+ * Which ids describe which rows: env_cycle_many renders the observation of the population as it stands when the cycle STARTS, then steps
+ * and compacts.  The ids (and env_num_many's counts) of the rows a cycle's render writes are therefore the ones taken BEFORE that cycle. */
+int env_info_many(EnvHandle *games, int n_env, int n_group, const char *name, void **out, void *stream);
 /* wait until everything enqueued on the environment's stream has finished */
 int env_sync(EnvHandle game);
 /* the environment's hipStream_t, as an opaque pointer (for event timing / interop by the caller) */

@@ -92,7 +92,9 @@ class DeepRecurrentQNetwork(BaseModel):
     # ------------------------------------------------------------------ acting
     @property
     def agent_states(self):
-        """{agent id: GRU state [512]} after the last call; on the kernel path materialised from the device table when read"""
+        """{agent id: GRU state [512]} after the last call; on the kernel path materialised from the device table when read.
+        After a call with `segments` the keys are tuples, {(segment, agent id): state}: every world of a packed batch has its own ids.
+        Rows in no segment have no entry.  The setter takes either form (an int key beside tuple keys is segment 0's)."""
         if self._agent_states is None:
             return self._hip.states_dict()
         return self._agent_states
@@ -111,9 +113,24 @@ class DeepRecurrentQNetwork(BaseModel):
             return self.bf16_kernels and tuple(view.shape) == (n,) + self.view_space[:2] + (8,)
         return view.dtype == torch.float32 and tuple(view.shape) == (n,) + self.view_space
 
+    def forget_segments(self, segments):
+        """forgets the states of these segments (ints) of the segmented calls: a world of the batch that was reset numbers its agents
+        from 0 again, and they start from zeros.  On the kernel path the device table is rewritten without a host wait."""
+        segments = set(int(s) for s in segments)
+        if self._agent_states is None:
+            self._hip.forget_segments(segments)
+        else:
+            self._agent_states = {k: v for k, v in self._agent_states.items() if (k[0] if isinstance(k, tuple) else 0) not in segments}
+
     @torch.no_grad()
-    def infer_action(self, raw_obs, ids, policy="e_greedy", eps=0):
-        """epsilon-greedy actions; the recurrent state of every agent is carried from its previous call by id"""
+    def infer_action(self, raw_obs, ids, policy="e_greedy", eps=0, segments=None):
+        """epsilon-greedy actions; the recurrent state of every agent is carried from its previous call by id.
+
+        segments: an int array [n_seg][2] of (begin, count) rows -- the worlds of a packed EnvBatch buffer (EnvBatch.packed_segments),
+        with `ids` the packed ids (EnvBatch.agent_ids).  The states are then keyed by (segment, id): segment s of the call is world s, and
+        every world has its own ids.  A row in no segment (a pad row, a stale row) starts from zeros; its action is returned and its
+        state is not stored.  States kept by plain calls are segment 0's; a plain call after a segmented one keeps segment 0's.  The
+        table is validated (ValueError naming the segment).  None: the call as it ever was."""
         view, feature = raw_obs[0], raw_obs[1]
         n = len(ids)
         if n == 0:
@@ -124,19 +141,29 @@ class DeepRecurrentQNetwork(BaseModel):
                 self._hip.load_states(self._agent_states)
                 self._agent_states = None
             ids_dev = ids.to(view.device, torch.int32) if isinstance(ids, torch.Tensor) else torch.as_tensor(np.asarray(ids, dtype=np.int32)).to(view.device)
-            best = self._hip.infer(view, feature, ids_dev)
+            best = self._hip.infer(view, feature, ids_dev) if segments is None else self._hip.infer(view, feature, ids_dev, segments=segments)
         else:
             if isinstance(view, torch.Tensor) and view.dtype == torch.bfloat16:
                 # bf16 cells [n, H, W, 8] (channels, zeros, a constant 1) without the bf16 kernels: the channels go back to float32
                 view = view[..., :self.view_space[-1]].float()
                 if self._on_kernels(view, feature, n):
-                    return self.infer_action((view.contiguous(), feature), ids, policy, eps)
+                    return self.infer_action((view.contiguous(), feature), ids, policy, eps, segments)
             ids_host = ids.cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)
             zero = torch.zeros(_RecurrentQNet.STATE, device=self.device)
             prev = self.agent_states
-            states = torch.stack([prev.get(int(i), zero) for i in ids_host]).unsqueeze(0)
+            if segments is None:
+                if any(isinstance(k, tuple) for k in prev):      # (after a segmented call: segment 0's states under their ids)
+                    prev = {(k[1] if isinstance(k, tuple) else k): v for k, v in prev.items() if not isinstance(k, tuple) or k[0] == 0}
+                keys = [int(i) for i in ids_host]
+            else:
+                from . import hip_policy
+                prev = {(k if isinstance(k, tuple) else (0, k)): v for k, v in prev.items()}
+                keys = [None] * n                                # (None: a row in no segment)
+                for s, (b, c) in enumerate(hip_policy.check_segments(segments, n).tolist()):
+                    keys[b:b + c] = [(s, int(i)) for i in ids_host[b:b + c]]
+            states = torch.stack([prev.get(k, zero) for k in keys]).unsqueeze(0)
             q, states = self.qnet(self._tensor(view), self._tensor(feature), n, 1, states)
-            self.agent_states = {int(i): states[0, k] for k, i in enumerate(ids_host)}   # agents that are gone drop out
+            self.agent_states = {k: states[0, r] for r, k in enumerate(keys) if k is not None}   # agents that are gone drop out
             best = q.argmax(dim=1).to(torch.int32)
         if policy == "e_greedy":
             rnd = torch.randint(self.num_actions, best.shape, dtype=torch.int32, device=self.device)

@@ -303,8 +303,20 @@ class _DrqnPolicy(_Packed):
     The state table is the last call's output: its ids in call order, their states float32 [.][512] (row k: the k-th id's), and for the
     next call's lookup the ids sorted stably with their rows.  An id of the next call takes the state of its last occurrence in the table,
     any other id starts from zeros; ids absent from the call drop out (drqn.py: the dict path's semantics).  Both kernel paths keep this
-    one format: a table can be handed from one to the other (states_dict / load_states).  `lib`: _Packed."""
+    one format: a table can be handed from one to the other (states_dict / load_states).  `lib`: _Packed.
+
+    `segments` (infer): an int array [n_seg][2] of (begin, count) rows -- the worlds of a packed EnvBatch buffer (EnvBatch.packed_segments),
+    each numbering its agents from 0.  The table is then keyed by (segment, id): segment s of the call is world s, and the table's second
+    format holds int64 keys (segment << 32) | uint32(id) (`_keys` in call order, `_sorted` their stable sort) where the plain one holds
+    int32 ids.  One look-up launch (policy_drqn_lookup_seg*) over all n rows finds every row's previous state; the steps then run per
+    chunk through the *_rows entries (a chunk may cut a segment: rows are independent); one stable sort of the keys follows.  A segment's
+    rows have the bits of a plain call on those rows alone with that world's own table.  A row in no segment (pad, stale) starts from
+    zeros, its action is returned, and its state enters the table under NO_KEY, which no look-up produces and which sorts to the end:
+    nothing is dropped, so nothing waits for the host.  More than MAX_SEGMENTS segments: several look-ups, cut at segment boundaries.
+    Between the forms: a plain table read by a segmented call is segment 0's; a segmented table read by a plain call keeps segment 0's
+    entries and drops the rest (that conversion reads the keys back: it waits for the device once)."""
     STATE = 512
+    NO_KEY = 0x7FFFFFFFFFFFFFFF
     _abi = None
 
     def __init__(self, qnet, view_space, feature_space, n_action, device, chunk=131072, lib=None):
@@ -318,25 +330,71 @@ class _DrqnPolicy(_Packed):
     def clear(self):
         z = torch.zeros(0, dtype=torch.int32, device=self.device)
         self._ids, self._sorted, self._rows = z, z, z
+        self._keys = None                # (not None: the (segment, id) format -- _sorted is then int64, _ids None)
         self._states = torch.zeros((0, self.STATE), device=self.device)
 
     def _set_table(self, ids, states):
-        self._ids, self._states = ids, states
+        self._ids, self._states, self._keys = ids, states, None
         self._sorted, perm = torch.sort(ids, stable=True)
         self._rows = perm.to(torch.int32)
 
+    def _set_keyed_table(self, keys, states):
+        """the (segment, id) format: int64 keys in call order, their states"""
+        self._ids, self._states, self._keys = None, states, keys
+        self._sorted, perm = torch.sort(keys, stable=True)
+        self._rows = perm.to(torch.int32)
+
+    def _to_keyed(self):
+        """a plain table becomes segment 0's (no host wait)"""
+        if self._keys is None:
+            self._set_keyed_table(self._ids.to(torch.int64) & 0xFFFFFFFF, self._states)
+
+    def _to_plain(self):
+        """a (segment, id) table keeps segment 0's entries under their ids and drops the rest (waits for the device: the count)"""
+        if self._keys is not None:
+            keep = (self._keys >> 32) == 0
+            ids = self._keys[keep].view(torch.int32).reshape(-1, 2)[:, 0].contiguous()        # (the low word: little-endian)
+            self._set_table(ids, self._states[keep].contiguous())
+
+    def forget_segments(self, segments):
+        """the states of these segments (ints) are forgotten -- a world of the batch that was reset numbers its agents from 0 again, and they
+        start from zeros: the segments' keys become NO_KEY and the table is sorted again.  No host wait."""
+        segments = sorted(set(int(s) for s in segments))
+        if not segments or self._sorted.numel() == 0:
+            return
+        if self._keys is None:
+            if 0 in segments:
+                self.clear()
+            return
+        gone = torch.isin(self._keys >> 32, torch.tensor(segments, dtype=torch.int64, device=self._keys.device))
+        self._set_keyed_table(torch.where(gone, torch.full_like(self._keys, self.NO_KEY), self._keys), self._states)
+
     def states_dict(self):
-        """{id: state [512]} as the dict path keeps it (insertion in call order, a duplicated id's last row)"""
-        return {int(i): self._states[k] for k, i in enumerate(self._ids.tolist())}
+        """{id: state [512]} as the dict path keeps it (insertion in call order, a duplicated id's last row); after a segmented call
+        {(segment, id): state}, the rows in no segment left out"""
+        if self._keys is None:
+            return {int(i): self._states[k] for k, i in enumerate(self._ids.tolist())}
+        out = {}
+        for k, key in enumerate(self._keys.tolist()):
+            if key != self.NO_KEY:
+                low = key & 0xFFFFFFFF
+                out[(key >> 32, low - (1 << 32) if low >= (1 << 31) else low)] = self._states[k]
+        return out
 
     def load_states(self, mapping):
-        """the table from a {id: state} mapping (an empty one empties it)"""
+        """the table from a {id: state} or {(segment, id): state} mapping (an empty one empties it; with tuple keys, an int key is
+        segment 0's)"""
         if len(mapping) == 0:
             self.clear()
             return
-        ids = torch.tensor([int(k) for k in mapping.keys()], dtype=torch.int32, device=self.device)
         states = torch.stack([torch.as_tensor(v).to(self.device, torch.float32).reshape(self.STATE) for v in mapping.values()]).contiguous()
-        self._set_table(ids, states)
+        if any(isinstance(k, tuple) for k in mapping.keys()):
+            pairs = [k if isinstance(k, tuple) else (0, k) for k in mapping.keys()]
+            keys = torch.tensor([(int(s) << 32) | (int(i) & 0xFFFFFFFF) for s, i in pairs], dtype=torch.int64, device=self.device)
+            self._set_keyed_table(keys, states)
+        else:
+            ids = torch.tensor([int(k) for k in mapping.keys()], dtype=torch.int32, device=self.device)
+            self._set_table(ids, states)
 
     # ---- weights
     def _pack_recurrent(self, t, stamp, frag, x_order=None, round_to=None):
@@ -369,21 +427,48 @@ class _DrqnPolicy(_Packed):
         self._set_packed(t, w, stamp)
 
     # ---- one step
-    def _step(self, entry, view, feature, ids, want_q):
-        """the library's `entry` on every chunk of the call (all chunks read the same previous table), then the new table"""
+    def _step(self, entry, view, feature, ids, want_q, segments=None):
+        """the library's `entry` on every chunk of the call (all chunks read the same previous table), then the new table; with
+        `segments` the look-up launch, then `entry`_rows on every chunk"""
         assert view.device == feature.device == ids.device and view.device.type == self.device.type
         assert view.is_contiguous() and feature.is_contiguous() and feature.dtype == torch.float32
         assert ids.dtype == torch.int32 and view.shape[0] == feature.shape[0] == ids.shape[0]
-        call = getattr(self._lib, entry)
+        n, dev = view.shape[0], view.device
+        seg = None if segments is None else check_segments(segments, n)
+        call = getattr(self._lib, entry if seg is None else entry + "_rows")
         if self.stale():
             self.pack()
-        n, dev = view.shape[0], view.device
-        ids = ids.clone(memory_format=torch.contiguous_format)        # (the table keeps it: the caller's buffer may be reused)
         actions = torch.empty(n, dtype=torch.int32, device=dev)
         q = torch.empty((n, self.shape.n_action), dtype=torch.float32, device=dev) if want_q else None
         new_states = torch.empty((n, self.STATE), dtype=torch.float32, device=dev)
         self._grow_work(dev, getattr(self._lib, self._abi[1]), min(n, self.chunk))
         stream = _stream(dev)
+        if seg is not None:
+            self._to_keyed()
+            ids = ids.contiguous()
+            count = int(self._sorted.numel())
+            from_row = torch.empty(n, dtype=torch.int32, device=dev)
+            keys = torch.empty(n, dtype=torch.int64, device=dev)
+            lookup = getattr(self._lib, self._abi[2])
+            for k in (range(0, len(seg), MAX_SEGMENTS) or [0]):      # one look-up per MAX_SEGMENTS segments, cut at segment boundaries:
+                part = seg[k:k + MAX_SEGMENTS]                       # rows from its first segment's begin (the first: row 0) to the next's
+                r0 = 0 if k == 0 else int(part[0, 0])
+                r1 = n if k + MAX_SEGMENTS >= len(seg) else int(seg[k + MAX_SEGMENTS, 0])
+                if r1 > r0:
+                    begin = (ctypes.c_int32 * max(len(part), 1))(*(part[:, 0] - r0).tolist())
+                    cnt = (ctypes.c_int32 * max(len(part), 1))(*part[:, 1].tolist())
+                    rc = lookup(ids[r0:].data_ptr(), r1 - r0, begin, cnt, len(part), k, _ptr(self._sorted if count else None),
+                                _ptr(self._rows if count else None), count, from_row[r0:].data_ptr(), keys[r0:].data_ptr(), stream)
+                    if rc != 0:
+                        raise RuntimeError("%s failed (%d)" % (self._abi[2], rc))
+            states = self._states.data_ptr() if count else None
+            self._chunked(entry + "_rows", n, self.chunk, lambda beg, m: call(
+                ctypes.byref(self.shape), ctypes.byref(self._w), view[beg:].data_ptr(), feature[beg:].data_ptr(), m, from_row[beg:].data_ptr(),
+                states, new_states[beg:].data_ptr(), self._work.data_ptr(), actions[beg:].data_ptr(), _ptr(q[beg:] if want_q else None), stream))
+            self._set_keyed_table(keys, new_states)
+            return (actions, q) if want_q else actions
+        self._to_plain()
+        ids = ids.clone(memory_format=torch.contiguous_format)        # (the table keeps it: the caller's buffer may be reused)
         count = int(self._sorted.numel())
         table = (self._sorted.data_ptr(), self._rows.data_ptr(), self._states.data_ptr()) if count else (None, None, None)
         self._chunked(entry, n, self.chunk, lambda beg, m: call(
@@ -398,7 +483,7 @@ class HipDrqnPolicyF32(_DrqnPolicy):
     """one acting step of a _RecurrentQNet in float32 -- the DQN's trunk (k_dqn_conv_f32 + k_dqn_head_f32), a GRU(512) cell (k_drqn_gru_f32),
     the head and argmax (k_drqn_head_f32): magent_amd/csrc/policy_drqn_f32.hip -- and the GRU state of every agent id in device memory
     (_DrqnPolicy)."""
-    _abi = ("policy_drqn_f32_supported", "policy_drqn_f32_workspace_bytes")
+    _abi = ("policy_drqn_f32_supported", "policy_drqn_f32_workspace_bytes", "policy_drqn_lookup_seg_f32")
 
     @torch.no_grad()
     def pack(self):
@@ -406,18 +491,19 @@ class HipDrqnPolicyF32(_DrqnPolicy):
         self._pack_recurrent(_trunk_f32(self.qnet, self.shape, self.device), stamp, fragment_order_f32)
 
     @torch.no_grad()
-    def infer(self, view, feature, ids, want_q=False):
+    def infer(self, view, feature, ids, want_q=False, segments=None):
         """view float32 [n][H][W][C], feature float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.
-        Enqueues the step on torch's current stream and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+        Enqueues the step on torch's current stream and replaces the state table; returns int32 actions [n] (and Q [n][A]).
+        segments: the (begin, count) rows of the worlds of a packed call, each with its own ids (_DrqnPolicy); None: the plain call"""
         assert view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c
-        return self._step("policy_drqn_infer_f32", view, feature, ids, want_q)
+        return self._step("policy_drqn_infer_f32", view, feature, ids, want_q, segments)
 
 
 class HipDrqnPolicy(_DrqnPolicy):
     """one acting step of a _RecurrentQNet with bf16 matrix operands -- the bf16 DQN's trunk (k_dqn_conv + k_dqn_head stopped after the
     hidden layer), the GRU cell (k_drqn_gru_bf16), the head and argmax (k_drqn_head_bf16): magent_amd/csrc/policy_drqn_bf16.hip.  Gates,
     blend and the state table are float32 (_DrqnPolicy): the rounding points are listed in include/magent_policy.h."""
-    _abi = ("policy_drqn_supported", "policy_drqn_workspace_bytes")
+    _abi = ("policy_drqn_supported", "policy_drqn_workspace_bytes", "policy_drqn_lookup_seg")
 
     @torch.no_grad()
     def pack(self):
@@ -426,13 +512,13 @@ class HipDrqnPolicy(_DrqnPolicy):
         self._pack_recurrent(t, stamp, fragment_order, x_order=hidden, round_to=torch.bfloat16)
 
     @torch.no_grad()
-    def infer(self, view, feature, ids, want_q=False):
+    def infer(self, view, feature, ids, want_q=False, segments=None):
         """view float32 [n][H][W][C] -- or bfloat16 [n][H][W][8], the engine's cells (GridWorld.get_observation_device_bf16) --, feature
         float32 [n][F] (contiguous, on the policy's device), ids int32 [n] on that device.  Enqueues the step on torch's current stream
-        and replaces the state table; returns int32 actions [n] (and Q [n][A])"""
+        and replaces the state table; returns int32 actions [n] (and Q [n][A]).  segments: as HipDrqnPolicyF32.infer"""
         cells16 = view.dtype == torch.bfloat16
         assert (cells16 and view.shape[-1] == 8) or (view.dtype == torch.float32 and view.shape[-1] == self.shape.view_c)
-        return self._step("policy_drqn_infer_bf16" if cells16 else "policy_drqn_infer", view, feature, ids, want_q)
+        return self._step("policy_drqn_infer_bf16" if cells16 else "policy_drqn_infer", view, feature, ids, want_q, segments)
 
 
 # ---------------------------------------------------------------------------------------------------- the actor-critic (a2c.py)

@@ -49,6 +49,7 @@ DEVICE_ABI = [
     ("env_cycle_many_cells", [_c.POINTER(_vp), _i, _i, _c.POINTER(_vp), _c.POINTER(_c.c_ubyte), _c.POINTER(_vp), _c.POINTER(_vp), _c.POINTER(_vp), _ip, _i]),
     ("env_cycle_pool_stats", [_c.POINTER(_c.c_longlong)]),
     ("env_num_many", [_c.POINTER(_vp), _i, _i, _ip]),
+    ("env_info_many", [_c.POINTER(_vp), _i, _i, _cp, _c.POINTER(_vp), _vp]),
     ("env_sync", [_vp]),
     ("env_get_stream", [_vp, _c.POINTER(_vp)]),
     ("env_streams_many", [_c.POINTER(_vp), _i, _c.POINTER(_vp)]),
@@ -79,7 +80,14 @@ POLICY_ABI = [
     ("policy_a2c_workspace_bytes", [_vp, _i, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_a2c_infer", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("policy_a2c_infer_bf16", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # the segmented forms: the plain arguments, then seg_begin, seg_count (host int arrays) and n_seg
+    # the segmented DRQN step: the look-up (ids, n, seg_begin, seg_count, n_seg, seg_first, prev_sorted_keys, rows, count, from_row, keys,
+    # stream), then the plain entries with (ids, prev_sorted_ids, rows, states, count) replaced by (from_row, states)
+    ("policy_drqn_lookup_seg_f32", [_vp, _i, _ip, _ip, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("policy_drqn_lookup_seg", [_vp, _i, _ip, _ip, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    ("policy_drqn_infer_f32_rows", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("policy_drqn_infer_rows", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("policy_drqn_infer_bf16_rows", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the segmented A2C forms: the plain arguments, then seg_begin, seg_count (host int arrays) and n_seg
     ("policy_a2c_f32_workspace_bytes_seg", [_vp, _i, _i, _i, _c.POINTER(_c.c_size_t)]),
     ("policy_a2c_infer_f32_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
     ("policy_a2c_workspace_bytes_seg", [_vp, _i, _i, _i, _c.POINTER(_c.c_size_t)]),

@@ -143,6 +143,8 @@ public:
     void set_action_device(int g, const int *d_act);
     void get_reward_device(int g, float *out);
     void info_device(int g, const char *name, void *out);
+    // info_device(g, "id", .) of n_group groups of n_env environments on the caller's stream, one launch per INFO_ITEMS items (env_info_many)
+    static void info_many(Env **envs, int n_env, int n_group, const char *name, void **out, hipStream_t st);
     // one environment cycle -- observe + set_action per group, step, rewards, clear_dead (examples/train_battle.py:61-109) --
     // in two launches for small worlds (k_render_multi, k_step_solo); NULL entries skip that call for that group
     // (cells: per group, non-zero where `view` is a bf16-cell buffer as observe_device's cells16 takes it; nullptr: float32 everywhere)

@@ -182,6 +182,34 @@ void Env::info_device(int g, const char *name, void *out) {
     else fatal("unsupported info name in get_info_device : %s", name);
 }
 
+// env_info_many: info_device(g, "id", out[e * n_group + g]) of every group of every environment, enqueued on the CALLER's stream `st` as
+// one launch per INFO_ITEMS non-empty items (launch.h).  Per environment what info_device does before it reads groups[g].cur; a null
+// entry and an empty group are no item.  No allocation, no copy, no host wait.
+void Env::info_many(Env **envs, int n_env, int n_group, const char *name, void **out, hipStream_t st) {
+    if (std::string(name ? name : "") != "id") fatal("unsupported info name in env_info_many : %s", name ? name : "(null)");
+    InfoItems T{};
+    int max_n = 0;
+    auto flush = [&]() {
+        launch_get_ids_many(st, T, max_n);
+        T.count = 0; max_n = 0;
+    };
+    for (int e = 0; e < n_env; e++) {
+        Env &env = *envs[e];
+        if (n_group > (int)env.groups.size()) fatal("invalid group handle in get_info : %d", n_group - 1);
+        env.use_device();
+        for (int g = 0; g < n_group; g++) {
+            void *dst = out[e * n_group + g];
+            const int n = env.groups[g].n;
+            if (!dst || n == 0) continue;
+            T.src[T.count] = env.groups[g].cur.id; T.dst[T.count] = (int *)dst; T.n[T.count] = n;
+            max_n = std::max(max_n, n);
+            if (++T.count == INFO_ITEMS) flush();
+        }
+    }
+    flush();
+    HIP_OK(hipGetLastError());
+}
+
 // GridWorld::get_info (GridWorld.cc:709-894)
 void Env::info_host(int g, const char *name, void *buf) {
     std::string k(name);

@@ -177,6 +177,11 @@ void launch_finish(hipStream_t s, const WorldView &W);
 void launch_get_reward(hipStream_t s, const GroupDev &G, float group_reward, float *out);
 void launch_get_pos(hipStream_t s, const GroupDev &G, int *out);
 void launch_get_alive(hipStream_t s, const GroupDev &G, unsigned char *out);
+// the ids of many (environment, group) items in one launch (env_info_many): the item table travels by value in the kernel's arguments --
+// 20 bytes an item, INFO_ITEMS of them and the count are 3844 bytes, under the 4 KB a launch's arguments may take
+constexpr int INFO_ITEMS = 192;
+struct InfoItems { const int *src[INFO_ITEMS]; int *dst[INFO_ITEMS]; int n[INFO_ITEMS]; int count; };
+void launch_get_ids_many(hipStream_t s, const InfoItems &items, int max_n);
 // clear_dead for every group in three launches (count, compact / init_reward, reset + device tables)
 struct ClearArgs {
     int mode[MAXG];        // 0 nothing (empty group), 1 Agent::init_reward only, 2 compaction of the survivors

@@ -62,6 +62,7 @@ struct GruArgs {
     const int *prev_ids;      // [count] the previous call's ids, ascending (equal ids in that call's order)
     const int *rows;          // [count] their rows of `states`
     const float *states;      // [.][512] the previous call's output states, float32
+    const int *from_row;      // [n] or null; not null (the *_rows entries): agent i's row of `states`, < 0 none -- ids, prev_ids, rows are not read
     int count, n, groups;     // groups: agent groups of 32 GRU_WAVES
     const bf16x8 *w;          // [64 k-steps][16 tiles][3 gates][64]: K = x's 512 slots, then h's 512 units; gates r, z, n
     const float *bias;        // [4][512] b_ir + b_hr, b_iz + b_hz, b_in, b_hn
@@ -79,7 +80,13 @@ __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_bf16(GruArgs A) {
     const int tile0 = (group * GRU_WAVES + w) * 32;
     if (group >= A.groups || tile0 >= A.n) return;               // (whole waves: the MFMAs below see every lane)
     const int agent = min(tile0 + r32, A.n - 1);
-    const float *hrow = HAS_H ? state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE) : nullptr;
+    const float *hrow = nullptr;
+    if (HAS_H) {
+        if (A.from_row) {                                        // (uniform: the look-up ran in its own launch, policy_drqn_lookup_seg)
+            const int row = A.from_row[agent];
+            hrow = row >= 0 ? A.states + (size_t)row * STATE : nullptr;
+        } else hrow = state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE);
+    }
     const bool have = hrow != nullptr;
     const bf16x8 *xp = A.x + (size_t)agent * (STATE / 8) + g;                 // k-step s: xp[2 s] = x[16 s + 8 g .. + 7]
     const f32x4 *hp = have ? (const f32x4 *)hrow + 2 * g : (const f32x4 *)xp; // k-step s: hp[4 s], hp[4 s + 1] = h[16 s + 8 g .. + 7]
@@ -179,13 +186,18 @@ __global__ void __launch_bounds__(QH_THREADS) k_drqn_head_bf16(QHeadArgs A) {
 }
 
 static size_t x_offset(const PolicyDqnShape *s, int n) { return magent_amd::drqn_x_offset(policy_dqn_act_bytes, s, n); }      // policy_host.h
+struct LookupBf16;        // (the tag of this file family's copy of k_drqn_lookup_seg)
 
+// All five entries.  The state of agent i: the id table's look-up (from_row null; count == 0: an empty table), or row from_row[i] of
+// `states` (rows_form, the *_rows entries; states null: an empty table).
 static int drqn_infer(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const void *view_any, bool cells16, const float *feat, int n,
-                      const int *ids, const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states,
-                      void *workspace, int *actions, float *q, void *stream) {
-    if (!policy_drqn_supported(s) || count < 0 || (count > 0 && !(prev_sorted_ids && rows && states))) return 1;
+                      const int *ids, const int *prev_sorted_ids, const int *rows, bool rows_form, const int *from_row, const float *states,
+                      int count, float *new_states, void *workspace, int *actions, float *q, void *stream) {
+    if (!policy_drqn_supported(s)) return 1;
+    if (!rows_form && (count < 0 || (count > 0 && !(prev_sorted_ids && rows && states)))) return 1;
     if (n <= 0) return 0;
-    if (!view_any || !feat || !ids || !new_states || !actions || !workspace) return 1;
+    if (!view_any || !feat || !(rows_form ? (const void *)from_row : (const void *)ids) || !new_states || !actions || !workspace) return 1;
+    const bool has_h = rows_form ? states != nullptr : count > 0;
     if (((uintptr_t)new_states | (uintptr_t)states | (uintptr_t)workspace) & 15) return 1;      // (rows are read and written as float4)
     if (cells16 && ((uintptr_t)view_any & 15)) return 1;                                         // (a cell is one 16-byte load)
     void *x = (char *)workspace + x_offset(s, n);
@@ -195,11 +207,12 @@ static int drqn_infer(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const
     magent_amd::StreamDevice on(st);
     if (!on.ok) return 2;
     GruArgs G{};
-    G.x = (const bf16x8 *)x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.count = count; G.n = n;
+    G.x = (const bf16x8 *)x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.from_row = rows_form ? from_row : nullptr;
+    G.count = count; G.n = n;
     G.groups = (n + 32 * GRU_WAVES - 1) / (32 * GRU_WAVES);
-    G.w = (const bf16x8 *)w->gru; G.bias = count > 0 ? w->gru_bias : w->gru_bias0; G.out = new_states;
+    G.w = (const bf16x8 *)w->gru; G.bias = has_h ? w->gru_bias : w->gru_bias0; G.out = new_states;
     const dim3 ggrid(xcd_grid(G.groups, GRU_TILES));
-    if (count > 0) hipLaunchKernelGGL(k_drqn_gru_bf16<true>, ggrid, dim3(GRU_THREADS), 0, st, G);
+    if (has_h) hipLaunchKernelGGL(k_drqn_gru_bf16<true>, ggrid, dim3(GRU_THREADS), 0, st, G);
     else hipLaunchKernelGGL(k_drqn_gru_bf16<false>, ggrid, dim3(GRU_THREADS), 0, st, G);
     QHeadArgs Q{};
     Q.h = new_states; Q.wh = (const bf16x8 *)w->head; Q.bh = w->head_bias; Q.n = n; Q.n_action = s->n_action; Q.dueling = w->dueling != 0;
@@ -223,13 +236,28 @@ int policy_drqn_workspace_bytes(const PolicyDqnShape *s, int n, size_t *bytes) {
 int policy_drqn_infer(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const float *view, const float *feat, int n, const int *ids,
                       const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states, void *workspace,
                       int *actions, float *q, void *stream) {
-    return drqn_infer(s, w, view, false, feat, n, ids, prev_sorted_ids, rows, states, count, new_states, workspace, actions, q, stream);
+    return drqn_infer(s, w, view, false, feat, n, ids, prev_sorted_ids, rows, false, nullptr, states, count, new_states, workspace, actions, q, stream);
 }
 
 int policy_drqn_infer_bf16(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const void *view_cells, const float *feat, int n, const int *ids,
                            const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states, void *workspace,
                            int *actions, float *q, void *stream) {
-    return drqn_infer(s, w, view_cells, true, feat, n, ids, prev_sorted_ids, rows, states, count, new_states, workspace, actions, q, stream);
+    return drqn_infer(s, w, view_cells, true, feat, n, ids, prev_sorted_ids, rows, false, nullptr, states, count, new_states, workspace, actions, q, stream);
+}
+
+int policy_drqn_lookup_seg(const int *ids, int n, const int *seg_begin, const int *seg_count, int n_seg, int seg_first,
+                           const long long *prev_sorted_keys, const int *rows, int count, int *from_row, long long *keys, void *stream) {
+    return magent_amd::drqn_lookup_seg<LookupBf16>(ids, n, seg_begin, seg_count, n_seg, seg_first, prev_sorted_keys, rows, count, from_row, keys, stream);
+}
+
+int policy_drqn_infer_rows(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const float *view, const float *feat, int n, const int *from_row,
+                           const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream) {
+    return drqn_infer(s, w, view, false, feat, n, nullptr, nullptr, nullptr, true, from_row, states, 0, new_states, workspace, actions, q, stream);
+}
+
+int policy_drqn_infer_bf16_rows(const PolicyDqnShape *s, const PolicyDrqnWeights *w, const void *view_cells, const float *feat, int n,
+                                const int *from_row, const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream) {
+    return drqn_infer(s, w, view_cells, true, feat, n, nullptr, nullptr, nullptr, true, from_row, states, 0, new_states, workspace, actions, q, stream);
 }
 
 }  // extern "C"

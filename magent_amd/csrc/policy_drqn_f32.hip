@@ -52,6 +52,7 @@ struct GruArgs {
     const int *prev_ids;      // [count] the previous call's ids, ascending (equal ids in that call's order)
     const int *rows;          // [count] their rows of `states`
     const float *states;      // [.][512] the previous call's output states
+    const int *from_row;      // [n] or null; not null (the *_rows entry): agent i's row of `states`, < 0 none -- ids, prev_ids, rows are not read
     int count, n;
     const f32x4 *w;           // [128 groups][16 tiles][3 gates][64]: K = x's 512, then h's 512; gates r, z, n
     const float *bias;        // [4][512] b_ir + b_hr, b_iz + b_hz, b_in, b_hn
@@ -65,7 +66,13 @@ __global__ void __launch_bounds__(GRU_THREADS) k_drqn_gru_f32(GruArgs A) {
     if (tile0 >= A.n) return;                                    // (whole waves: the MFMAs below see every lane)
     const int T = blockIdx.y;
     const int agent = min(tile0 + r32, A.n - 1);
-    const float *hrow = HAS_H ? state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE) : nullptr;
+    const float *hrow = nullptr;
+    if (HAS_H) {
+        if (A.from_row) {                                        // (uniform: the look-up ran in its own launch, policy_drqn_lookup_seg_f32)
+            const int row = A.from_row[agent];
+            hrow = row >= 0 ? A.states + (size_t)row * STATE : nullptr;
+        } else hrow = state_row(A.ids[agent], A.prev_ids, A.rows, A.count, A.states, STATE);
+    }
     const bool have = hrow != nullptr;
     const f32x4 *xp = (const f32x4 *)(A.x + (size_t)agent * STATE) + g;       // group m: xp[2 m] = x[8 m + 4 g .. + 3]
     const f32x4 *hp = have ? (const f32x4 *)hrow + g : xp;                    // (a lane without a state reads x and takes zeros)
@@ -158,12 +165,16 @@ int policy_drqn_f32_workspace_bytes(const PolicyDqnShape *s, int n, size_t *byte
     return 0;
 }
 
-int policy_drqn_infer_f32(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w, const float *view, const float *feat, int n, const int *ids,
-                          const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states, void *workspace,
-                          int *actions, float *q, void *stream) {
-    if (!policy_drqn_f32_supported(s) || count < 0 || (count > 0 && !(prev_sorted_ids && rows && states))) return 1;
-    if (n <= 0) return 0;
-    if (!ids || !new_states || !actions || !workspace) return 1;
+}  // extern "C"
+
+namespace {
+
+// Both entries behind their argument checks.  The state of agent i: the id table's look-up (from_row null; count == 0: an empty table),
+// or row from_row[i] of `states` (the *_rows entry; states null: an empty table).
+int drqn_infer_f32(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w, const float *view, const float *feat, int n, const int *ids,
+                   const int *prev_sorted_ids, const int *rows, const int *from_row, const float *states, int count, float *new_states,
+                   void *workspace, int *actions, float *q, void *stream) {
+    const bool has_h = from_row ? states != nullptr : count > 0;
     if (((uintptr_t)new_states | (uintptr_t)states | (uintptr_t)workspace) & 15) return 1;      // (rows are read and written as float4)
     float *x = (float *)((char *)workspace + x_offset(s, n));
     int rc = magent_amd::f32::dqn_f32_trunk(s, &w->trunk, view, feat, n, workspace, x, stream);
@@ -172,16 +183,44 @@ int policy_drqn_infer_f32(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w
     magent_amd::StreamDevice on(st);
     if (!on.ok) return 2;
     GruArgs G{};
-    G.x = x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.count = count; G.n = n;
-    G.w = (const f32x4 *)w->gru; G.bias = count > 0 ? w->gru_bias : w->gru_bias0; G.out = new_states;
+    G.x = x; G.ids = ids; G.prev_ids = prev_sorted_ids; G.rows = rows; G.states = states; G.from_row = from_row; G.count = count; G.n = n;
+    G.w = (const f32x4 *)w->gru; G.bias = has_h ? w->gru_bias : w->gru_bias0; G.out = new_states;
     const dim3 ggrid((n + 32 * GRU_WAVES - 1) / (32 * GRU_WAVES), GRU_TILES);
-    if (count > 0) hipLaunchKernelGGL(k_drqn_gru_f32<true>, ggrid, dim3(GRU_THREADS), 0, st, G);
+    if (has_h) hipLaunchKernelGGL(k_drqn_gru_f32<true>, ggrid, dim3(GRU_THREADS), 0, st, G);
     else hipLaunchKernelGGL(k_drqn_gru_f32<false>, ggrid, dim3(GRU_THREADS), 0, st, G);
     QHeadArgs Q{};
     Q.h = new_states; Q.wh = (const f32x4 *)w->head; Q.bh = w->head_bias; Q.n = n; Q.n_action = s->n_action; Q.dueling = w->dueling != 0;
     Q.actions = actions; Q.q = q;
     hipLaunchKernelGGL(k_drqn_head_f32, dim3((n + 32 * QH_WAVES - 1) / (32 * QH_WAVES)), dim3(QH_THREADS), 0, st, Q);
     return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+struct LookupF32;         // (the tag of this file family's copy of k_drqn_lookup_seg)
+
+}  // namespace
+
+extern "C" {
+
+int policy_drqn_infer_f32(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w, const float *view, const float *feat, int n, const int *ids,
+                          const int *prev_sorted_ids, const int *rows, const float *states, int count, float *new_states, void *workspace,
+                          int *actions, float *q, void *stream) {
+    if (!policy_drqn_f32_supported(s) || count < 0 || (count > 0 && !(prev_sorted_ids && rows && states))) return 1;
+    if (n <= 0) return 0;
+    if (!ids || !new_states || !actions || !workspace) return 1;
+    return drqn_infer_f32(s, w, view, feat, n, ids, prev_sorted_ids, rows, nullptr, states, count, new_states, workspace, actions, q, stream);
+}
+
+int policy_drqn_lookup_seg_f32(const int *ids, int n, const int *seg_begin, const int *seg_count, int n_seg, int seg_first,
+                               const long long *prev_sorted_keys, const int *rows, int count, int *from_row, long long *keys, void *stream) {
+    return magent_amd::drqn_lookup_seg<LookupF32>(ids, n, seg_begin, seg_count, n_seg, seg_first, prev_sorted_keys, rows, count, from_row, keys, stream);
+}
+
+int policy_drqn_infer_f32_rows(const PolicyDqnShape *s, const PolicyDrqnWeightsF32 *w, const float *view, const float *feat, int n,
+                               const int *from_row, const float *states, float *new_states, void *workspace, int *actions, float *q, void *stream) {
+    if (!policy_drqn_f32_supported(s)) return 1;
+    if (n <= 0) return 0;
+    if (!from_row || !new_states || !actions || !workspace) return 1;
+    return drqn_infer_f32(s, w, view, feat, n, nullptr, nullptr, nullptr, from_row, states, 0, new_states, workspace, actions, q, stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 //   policy_epilogue                                  softmax, clamp, the stores and the inverse-CDF draw (k_a2c_head_f32, k_a2c_head_bf16)
 //   pingpong                                         the streamed-row double buffering (k_drqn_gru_f32, k_a2c_layer_f32, head_gemm512_bf16)
 //   state_row                                        the id table's look-up (k_drqn_gru_f32, k_drqn_gru_bf16)
+//   drqn_key, state_row_of_key, drqn_lookup_row      the (segment, id) table's look-up (policy_host.h: k_drqn_lookup_seg)
 //   colsum_rows, colsum_blocks                       the CommNet column sums' bodies (policy_host.h: the k_a2c_colsum* kernels)
 //   seg_map, colsum_part_seg, colsum_blocks_seg, seg_of_row   the segmented A2C call's maps and sums (k_a2c_segmap, the *_seg kernels, the layers)
 // The bf16 files take their float32 side from here too (policy_bf16_dev.h includes this header): policy.hip the vector types, out_of
@@ -296,6 +297,47 @@ __device__ __forceinline__ const float *state_row(int id, const int *prev_ids, c
         else hi = mid;
     }
     return lo > 0 && prev_ids[lo - 1] == id ? states + (size_t)rows[lo - 1] * pitch : nullptr;
+}
+
+// The segmented call's table (policy_drqn_lookup_seg*): the key of agent `id` of segment `seg` is (seg << 32) | uint32(id) -- every world
+// of a packed batch numbers its agents from 0, the segment keeps them apart.  A row in no segment (a pad row, a stale row) takes
+// DRQN_NO_KEY, which no look-up produces (segment 2^31 - 1 is refused) and which sorts behind every key: such rows stay in the table,
+// at its end, and nobody finds them.
+constexpr long long DRQN_NO_KEY = 0x7FFFFFFFFFFFFFFFLL;
+__device__ __forceinline__ long long drqn_key(int seg, int id) { return (long long)(((unsigned long long)(unsigned)seg << 32) | (unsigned)id); }
+// state_row's search on the 64-bit keys: the row of `states` of the LAST entry of prev_keys (ascending; equal keys in that call's order)
+// equal to key, or -1
+__device__ __forceinline__ int state_row_of_key(long long key, const long long *prev_keys, const int *rows, int count) {
+    int lo = 0, hi = count;                                      // lo: the first entry above key
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (prev_keys[mid] <= key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && prev_keys[lo - 1] == key ? rows[lo - 1] : -1;
+}
+// One row of the look-up launch: its segment is the last one that begins at or in front of it, if the row is inside it (the table
+// ascends without overlap: an empty segment in front of it with the same begin is passed over).  from_row[r]: the row of the previous
+// call's states that holds this agent's state, -1 for an agent the table does not know and for a row in no segment; keys[r]: its key in
+// THIS call's table.  seg_first: the number of the table's segment 0 among the call's segments (a call of more than A2C_MAX_SEGMENTS
+// segments goes through several look-ups).
+__device__ __forceinline__ void drqn_lookup_row(int r, const int *ids, const A2cSegTable &t, int seg_first, const long long *prev_keys,
+                                                const int *rows, int count, int *from_row, long long *keys) {
+    int lo = 0, hi = t.n_seg;                                    // lo: the first segment that begins behind r
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t.begin[mid] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    const int s = lo - 1;
+    if (s < 0 || r >= t.begin[s] + t.count[s]) {
+        from_row[r] = -1;
+        keys[r] = DRQN_NO_KEY;
+        return;
+    }
+    const long long key = drqn_key(seg_first + s, ids[r]);
+    from_row[r] = state_row_of_key(key, prev_keys, rows, count);
+    keys[r] = key;
 }
 
 // ---------------------------------------------------------------------------------------------------- column sums in a fixed order

@@ -56,6 +56,37 @@ inline size_t drqn_x_offset(int (*act_bytes)(const PolicyDqnShape *, int, size_t
     return (act + 255) / 256 * 256;
 }
 
+inline bool a2c_seg_table(const int *seg_begin, const int *seg_count, int n_seg, int n, A2cSegTable *out);      // (below, with the A2C's segmented call)
+
+// ---- the segmented DRQN step (policy_drqn_lookup_seg*, then policy_drqn_infer*_rows): the state table is keyed by (segment, id)
+// (policy_f32_dev.h: drqn_key).  The look-up is a divergent binary search per lane; it runs in ONE small launch of its own over all rows
+// of the call, whatever the chunks the GRU steps are cut into afterwards, and the GRU kernels read the row it found.  The kernel is a
+// template of the file family's tag as the A2C's small kernels are of their row type: only a translation unit that launches it holds it.
+constexpr int DRQN_LK_THREADS = 256;
+template <class Tag>
+static __global__ void __launch_bounds__(DRQN_LK_THREADS) k_drqn_lookup_seg(A2cSegTable t, int n, const int *ids, int seg_first, const long long *prev_keys,
+                                                                           const int *rows, int count, int *from_row, long long *keys) {
+    const int r = blockIdx.x * DRQN_LK_THREADS + threadIdx.x;
+    if (r < n) f32::drqn_lookup_row(r, ids, t, seg_first, prev_keys, rows, count, from_row, keys);
+}
+// Both exported look-ups.  The table as the segmented A2C entries state it (a2c_seg_table: its format, validation and cap); 0; 1: a
+// refused argument (nothing is written); 2: the runtime refused the device; 3: the launch failed.
+template <class Tag>
+int drqn_lookup_seg(const int *ids, int n, const int *seg_begin, const int *seg_count, int n_seg, int seg_first, const long long *prev_sorted_keys,
+                    const int *rows, int count, int *from_row, long long *keys, void *stream) {
+    A2cSegTable table;
+    if (!a2c_seg_table(seg_begin, seg_count, n_seg, n, &table)) return 1;
+    if (seg_first < 0 || seg_first > 0x7FFFFFFF - A2C_MAX_SEGMENTS - 1 || count < 0 || (count > 0 && !(prev_sorted_keys && rows))) return 1;
+    if (n <= 0) return 0;
+    if (!ids || !from_row || !keys) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    StreamDevice on(st);
+    if (!on.ok) return 2;
+    hipLaunchKernelGGL(k_drqn_lookup_seg<Tag>, dim3((n + DRQN_LK_THREADS - 1) / DRQN_LK_THREADS), dim3(DRQN_LK_THREADS), 0, st, table, n, ids, seg_first,
+                       prev_sorted_keys, rows, count, from_row, keys);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
 // ---- the segmented A2C call (policy_a2c_infer*_seg): every CommNet mean runs over the rows of the agent's own segment.  k_a2c_segmap
 // writes what the other kernels read of the table (policy_f32_dev.h: A2cSegTable) into the workspace: no allocation, no copy, no host wait.
 // The table as the C-ABI states it: 0 <= n_seg <= the cap, begin and count >= 0, begin + count <= n, ascending and disjoint.

@@ -119,6 +119,13 @@ int env_num_many(EnvHandle *games, int n_env, int n_group, int *out) {
     }
     return 0;
 }
+// the agent ids of n_env environments x n_group groups in one launch on the caller's stream (a launch per INFO_ITEMS items; launch.h)
+int env_info_many(EnvHandle *games, int n_env, int n_group, const char *name, void **out, void *stream) {
+    std::vector<Env *> envs(n_env > 0 ? n_env : 0);
+    for (int e = 0; e < n_env; e++) envs[e] = E(games[e]);
+    Env::info_many(envs.data(), n_env, n_group, name, out, (hipStream_t)stream);
+    return 0;
+}
 // the streams of n_env environments in one call: out[2 e] = env_get_stream's, out[2 e + 1] = env_get_action_stream's
 int env_streams_many(EnvHandle *games, int n_env, void **out) {
     for (int e = 0; e < n_env; e++) { out[2 * e] = (void *)E(games[e])->stream; out[2 * e + 1] = (void *)E(games[e])->action_stream(); }

@@ -318,6 +318,15 @@ __global__ void __launch_bounds__(256) k_get_alive(GroupDev G, unsigned char *ou
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < G.n) out[i] = G.dead[i] ? 0 : 1;
 }
+// env_info_many: workgroup (x, item) copies rows 256 x, 256 (x + gridDim.x), ... of its item's ids (plain vector stores)
+__global__ void __launch_bounds__(256) k_get_ids_many(InfoItems T) {
+    const int item = blockIdx.y;
+    if (item >= T.count) return;
+    const int n = T.n[item];
+    const int *src = T.src[item];
+    int *dst = T.dst[item];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
 
 // ------------------------------------------------------------------------------------------------ clear_dead
 // Agent::init_reward for a group without deaths (no compaction needed)
@@ -794,6 +803,9 @@ void launch_get_pos(hipStream_t s, const GroupDev &G, int *out) {
 }
 void launch_get_alive(hipStream_t s, const GroupDev &G, unsigned char *out) {
     if (G.n > 0) hipLaunchKernelGGL(k_get_alive, dim3((G.n + 255) / 256), dim3(256), 0, s, G, out);
+}
+void launch_get_ids_many(hipStream_t s, const InfoItems &items, int max_n) {
+    if (items.count > 0 && max_n > 0) hipLaunchKernelGGL(k_get_ids_many, dim3(std::min((max_n + 255) / 256, 64), items.count), dim3(256), 0, s, items);
 }
 
 void launch_init_reward(hipStream_t s, const WorldView &W, int g) {

@@ -705,7 +705,11 @@ class EnvBatch(object):
     for them is ignored: the engine reads each segment's n actions only.  A network whose rows talk to each other -- the A2C's CommNet
     averages over the rows of a call -- needs to know where one environment ends: packed_segments() gives each group's (begin, count)
     table, and AdvantageActorCritic.infer_action(..., segments=table) keeps every mean inside its environment in ONE call per side; pad
-    rows and the stale rows behind a world's living agents act alone and enter no mean."""
+    rows and the stale rows behind a world's living agents act alone and enter no mean.  A network that keeps a state per agent id -- the
+    DRQN's GRU -- needs the ids, and every world numbers its agents from 0: agent_ids() writes all worlds' ids into a packed int32 buffer
+    in one launch, and DeepRecurrentQNetwork.infer_action(obs, ids, segments=table) keys its states by (world, id) in ONE call per side
+    (forget_segments([e]) after world e was reset).  cycle() renders the population as it stands when it starts: ids and table are the
+    ones taken BEFORE the cycle whose observations they describe (agent_ids)."""
 
     def __init__(self, envs, n_threads=8):
         self.envs, self.n_threads = list(envs), n_threads
@@ -798,6 +802,32 @@ class EnvBatch(object):
             self._nums = np.frombuffer(self._nums_c, dtype=np.int32).reshape(len(self.envs), self.n_group)
         self._lib.env_num_many(self._handles, len(self.envs), self.n_group, self._nums_c)
         return self._nums
+
+    def agent_ids(self, ids, stream=None):
+        """every (environment, group)'s agent ids -- get_info_device(handle, "id", .) -- in ONE launch for the whole batch (env_info_many;
+        a launch per 192 non-empty entries).  ids: a pointers() / packed_pointers() array of int32 tensors, or the nested list form;
+        entry [e][g] takes the n ids of group g of environment e, a None entry and an empty group take nothing, and rows behind the n
+        (pad rows, stale rows) are not written.  No allocation, no copy, no host wait.
+
+        Streams.  The copy is enqueued on torch's current stream, where a policy reads the ids (stream: another hipStream_t as an int).
+        With `order_streams` on, torch's stream is first ordered behind each distinct engine stream (order_torch_after); the next
+        cycle() orders the engine behind torch again.  With it off the caller synchronises: a nested list of CUDA tensors still goes
+        to torch's current stream, a pointer array to the null stream.
+
+        Which ids describe which rows.  cycle() renders the observation of the population as it stands when the cycle STARTS, then steps
+        and compacts.  The ids and counts (nums_array, packed_segments) of the rows a cycle's render writes are therefore the ones
+        taken BEFORE that cycle: call agent_ids and packed_segments, then cycle, then the policy on that cycle's observations."""
+        if stream is None:
+            dev = None
+            if not isinstance(ids, ctypes.Array):
+                dev = next((t.device for per_env in ids for t in per_env if t is not None), None)
+            if self.order_streams or (dev is not None and dev.type == "cuda"):
+                import torch
+                if self.order_streams:
+                    for e in self._distinct():
+                        e.order_torch_after()
+                stream = torch.cuda.current_stream(dev if dev is not None else torch.device("cuda", self.envs[0].device_id)).cuda_stream
+        self._lib.env_info_many(self._handles, len(self.envs), self.n_group, b"id", self._ptrs(ids), stream)
 
     def cycle(self, views=None, feats=None, actions=None, rewards=None, view_cells=None):
         """each argument: list (per env) of lists (per group) of CUDA tensors or None, or the result of pointers();
