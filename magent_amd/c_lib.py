@@ -94,6 +94,15 @@ POLICY_ABI = [
     ("policy_a2c_infer_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
     ("policy_a2c_infer_bf16_seg", [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _i]),
 ]
+# include/magent_replay.h: the device episode recorder (magent_amd/replay.py passes its ReplayState by reference)
+REPLAY_ABI = [
+    ("replay_find", [_vp, _vp, _i, _ip, _ip, _i, _vp, _vp, _i, _vp]),
+    ("replay_candidates", [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    ("replay_admit", [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    ("replay_step", [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    ("replay_copy", [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("replay_pack", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+]
 # include/magent_runtime_api.h PART 3, the rule-based actors: (name, restype, argtypes).  A table of its own, bound only where
 # the library exports it (the CPU checkers under oracle/ do not; `has_actor_api` says whether this one does).
 ACTOR_ABI = [
@@ -109,6 +118,19 @@ def declare_policy(lib):
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    return lib
+
+
+def declare_replay(lib):
+    """restype / argtypes of the REPLAY_ABI symbols of `lib` (also for the tests' emulated build of replay.hip); lib.has_replay_api says
+    whether it exports them all"""
+    lib.has_replay_api = True
+    for name, argtypes in REPLAY_ABI:
+        fn = getattr(lib, name, None)
+        if fn is None:
+            lib.has_replay_api = False
+            continue
+        fn.restype, fn.argtypes = ctypes.c_int, argtypes
     return lib
 
 
@@ -153,6 +175,7 @@ def _load(path=None):
             continue
         fn.restype, fn.argtypes = ctypes.c_int, argtypes
     declare_policy(lib)
+    declare_replay(lib)
     lib.has_actor_api = True
     for name, restype, argtypes in ACTOR_ABI:
         fn = getattr(lib, name, None)

@@ -1,5 +1,8 @@
 """Helpers around the engine used by the training scripts (mirror of the call surface of reference
-python/magent/utility.py: EpisodesBuffer, decay schedules, sample_observation, init_logger, rec_round)."""
+python/magent/utility.py: EpisodesBuffer, decay schedules, sample_observation, init_logger, rec_round).
+
+EpisodesBuffer is the host recorder of ONE world.  A packed EnvBatch is recorded on the device, without a host wait, by
+magent_amd.DeviceEpisodesBuffer (magent_amd/replay.py), which hands the models' train() the same packed() / episodes()."""
 import logging
 import math
 
