@@ -96,6 +96,21 @@ int replay_copy(const ReplayState *st, const int *counters, int call, int max_ro
 int replay_pack(const ReplayState *st, int n_trans, void *out_view, void *out_feat, int *out_act, float *out_rew, unsigned char *out_terminal,
                 float *out_mask, int *base, int *dst, void *stream);
 
+/* The A2C's discounted returns of the packed round, after replay_pack: `base` as replay_pack left it, rew float32 [n_trans] the packed
+ * rewards, boot float32 [n_slots] one bootstrap value per slot, out_ret float32 [n_trans] (not overlapping rew).  For every slot
+ * s < n_slots (<= capacity) with len[s] > 0:
+ *     keep = (double)boot[s];  for i = len[s] - 1 down to 0:  keep = keep * gamma + (double)rew[base[s] + i];  out_ret[base[s] + i] = (float)keep
+ * in IEEE double with the product and the sum rounded SEPARATELY (no fused multiply-add), rounded once to float32: bit for bit what
+ * AdvantageActorCritic.train computes on the host.  A slot of length 0 writes nothing and its boot entry is not read.  A NULL pointer,
+ * a negative count, n_slots > capacity or n_trans > max_transitions is refused (1); n_slots == 0 or n_trans == 0 returns 0 and writes
+ * nothing.
+ * replay_returns stages a workgroup's contiguous rows in LDS where they fit; replay_returns_direct is the same function with every lane
+ * on global memory (tools/a2c_train_rate.py times both). */
+int replay_returns(const ReplayState *st, int n_slots, int n_trans, const int *base, const float *rew, const float *boot, double gamma,
+                   float *out_ret, void *stream);
+int replay_returns_direct(const ReplayState *st, int n_slots, int n_trans, const int *base, const float *rew, const float *boot, double gamma,
+                          float *out_ret, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

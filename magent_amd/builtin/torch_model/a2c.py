@@ -136,10 +136,8 @@ class AdvantageActorCritic(BaseModel):
         acts = torch.multinomial(policy, 1).squeeze(1).to(torch.int32)
         return acts if isinstance(view, torch.Tensor) else acts.cpu().numpy()
 
-    def train(self, sample_buffer, print_every=1000):
-        """one gradient step over all samples of the round; returns ([pg_loss, vf_loss, ent_loss], mean state value)"""
-        if self._hip is not None:
-            self._hip.dirty = True            # (the parameters change below; the kernels' packed copy is rebuilt at the next call)
+    def _episodes_round(self, sample_buffer):
+        """(view, feature, action, returns) of the round from the buffer's episodes, one at a time; None: nothing recorded"""
         views, features, actions, returns = [], [], [], []
         for ep in sample_buffer.episodes():
             m = len(ep.rewards)
@@ -156,8 +154,35 @@ class AdvantageActorCritic(BaseModel):
             views.append(v); features.append(f)
             actions.append(self._tensor(np.asarray(ep.actions), torch.int64)); returns.append(self._tensor(r))
         if not views:
+            return None
+        return torch.cat(views), torch.cat(features), torch.cat(actions), torch.cat(returns)
+
+    def _packed_round(self, rec):
+        """the same four tensors from a device recorder (magent_amd.DeviceEpisodesBuffer) without a per-episode step: packed()'s rows are
+        the episodes' rows in slot order, as they are; the bootstrap values are ONE batched pass over every episode's last observation,
+        each row alone (the episodes route's one-row calls: no CommNet message); the recurrence runs on the device, rec.returns, bit for
+        bit the host loop's function of those values"""
+        p = rec.packed()
+        if p is None:
+            return None
+        view, feature = p[0], p[1]
+        slots, rows = rec.last_rows()
+        with torch.no_grad():
+            values = self.net(view[rows], feature[rows], alone=True)[1]
+        bootstrap = torch.zeros(rec.tracked, dtype=torch.float32, device=view.device)
+        bootstrap[slots] = values
+        return view, feature, p[2].to(torch.int64), rec.returns(bootstrap, self.reward_decay)
+
+    def train(self, sample_buffer, print_every=1000):
+        """one gradient step over all samples of the round; returns ([pg_loss, vf_loss, ent_loss], mean state value).  A buffer that
+        offers packed(), last_rows() and returns() (DeviceEpisodesBuffer) is read through them, any other through episodes()"""
+        if self._hip is not None:
+            self._hip.dirty = True            # (the parameters change below; the kernels' packed copy is rebuilt at the next call)
+        on_device = all(hasattr(sample_buffer, name) for name in ("packed", "last_rows", "returns"))
+        batch = self._packed_round(sample_buffer) if on_device else self._episodes_round(sample_buffer)
+        if batch is None:
             return [0.0, 0.0, 0.0], 0.0
-        view, feature, action, reward = torch.cat(views), torch.cat(features), torch.cat(actions), torch.cat(returns)
+        view, feature, action, reward = batch
         policy, value = self.net(view, feature)
         log_policy = torch.log(policy + 1e-6)
         log_prob = log_policy.gather(1, action.unsqueeze(1)).squeeze(1)

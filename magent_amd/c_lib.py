@@ -103,6 +103,11 @@ REPLAY_ABI = [
     ("replay_copy", [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("replay_pack", [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
+# the returns entries, newer than the rest: a library without them records and packs as before (`has_replay_returns`)
+REPLAY_RETURNS_ABI = [
+    ("replay_returns", [_vp, _i, _i, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    ("replay_returns_direct", [_vp, _i, _i, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+]
 # include/magent_runtime_api.h PART 3, the rule-based actors: (name, restype, argtypes).  A table of its own, bound only where
 # the library exports it (the CPU checkers under oracle/ do not; `has_actor_api` says whether this one does).
 ACTOR_ABI = [
@@ -123,14 +128,16 @@ def declare_policy(lib):
 
 def declare_replay(lib):
     """restype / argtypes of the REPLAY_ABI symbols of `lib` (also for the tests' emulated build of replay.hip); lib.has_replay_api says
-    whether it exports them all"""
+    whether it exports them all, lib.has_replay_returns whether it has replay_returns (DeviceEpisodesBuffer.returns)"""
     lib.has_replay_api = True
-    for name, argtypes in REPLAY_ABI:
+    for name, argtypes in REPLAY_ABI + REPLAY_RETURNS_ABI:
         fn = getattr(lib, name, None)
         if fn is None:
-            lib.has_replay_api = False
+            if (name, argtypes) in REPLAY_ABI:
+                lib.has_replay_api = False
             continue
         fn.restype, fn.argtypes = ctypes.c_int, argtypes
+    lib.has_replay_returns = getattr(lib, "replay_returns", None) is not None
     return lib
 
 

@@ -21,6 +21,8 @@
 //                        number of rows is read on the device.  The pack's scatter is the same kernel with the indices swapped.
 //   k_replay_base        exclusive scan of the episode lengths -> every slot's first row of the packed arrays
 //   k_replay_dst         log row j -> base[slot] + ordinal; terminal and mask from "ordinal == len - 1" and the died flag
+//   k_replay_returns     the A2C's discounted returns over the packed rewards: one lane per slot, from the episode's last row to its
+//                        first, keep = keep * gamma + r in double with the product and the sum rounded separately
 //
 // No floating-point atomics and no atomic whose result depends on the order (the one atomic is k_replay_find's integer maximum).
 #include <hip/hip_runtime.h>
@@ -37,6 +39,7 @@ namespace magent_amd {
 namespace {
 
 constexpr int RP_THREADS = 256, RP_SCAN = REPLAY_SCAN_BLOCK, RP_ADMIT_PER_THREAD = 8, RP_COPY_MAX_BLOCKS = 8192;
+constexpr int RP_RET_SLOTS = 128, RP_RET_LDS = 8192;            // k_replay_returns: slots per workgroup; the rows (float32) its LDS stage takes
 
 // Exclusive scan of v over the RP_SCAN threads of the workgroup, *total: the sum (Hillis-Steele on two LDS rows; buf: int [2 * RP_SCAN]).
 // Ends with a barrier: buf may be reused at once.
@@ -242,6 +245,60 @@ __global__ void __launch_bounds__(RP_THREADS) k_replay_copy(RowCopy c, const int
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- the discounted returns
+// One step of the A2C's recurrence in IEEE double, the product and the sum rounded separately, as the host's `keep * gamma + r[i]` is:
+// the pragma keeps the compiler from contracting the two into an FMA (device code is contracted by default).
+__device__ __forceinline__ double returns_step(double keep, double gamma, float r) {
+#pragma clang fp contract(off)
+    const double scaled = keep * gamma;
+    return scaled + (double)r;
+}
+
+// One lane per slot, serial inside the episode (a scan of composed affine maps would round differently).  A lane whose rows are not
+// inside the packed arrays -- a base that replay_pack did not leave -- writes nothing.
+//   STAGED: the packed rows of a workgroup's RP_RET_SLOTS consecutive slots are one contiguous range.  Where it is at most RP_RET_LDS
+//   rows, the rewards come into LDS coalesced, the lanes run the recurrence there (float32 overwritten in place, keep a double in a
+//   register) and the range leaves coalesced; a longer range takes the direct form, decided per workgroup.
+template <bool STAGED>
+__global__ void __launch_bounds__(RP_RET_SLOTS) k_replay_returns(ReplayState st, int n_slots, int n_trans, const int *__restrict__ base,
+                                                                const float *__restrict__ rew, const float *__restrict__ boot, double gamma,
+                                                                float *__restrict__ out) {
+    __shared__ float lds[STAGED ? RP_RET_LDS : 1];
+    const int s0 = blockIdx.x * RP_RET_SLOTS, s = s0 + threadIdx.x;
+    int b = 0, m = 0;
+    if (s < n_slots) {
+        b = base[s];
+        m = st.len[s];
+        if (m < 0 || b < 0 || (long long)b + m > (long long)n_trans) m = 0;
+    }
+    if (STAGED) {
+        const int s1 = min(s0 + RP_RET_SLOTS, n_slots) - 1;      // (s0 < n_slots: the grid covers n_slots)
+        const int lo = base[s0], hi = base[s1] + st.len[s1];
+        if (lo >= 0 && hi >= lo && hi <= n_trans && hi - lo <= RP_RET_LDS) {       // (the same words in every lane: no lane leaves the others at a barrier)
+            for (int i = threadIdx.x; i < hi - lo; i += RP_RET_SLOTS) lds[i] = rew[lo + i];
+            __syncthreads();
+            if (m > 0 && b >= lo && b + m <= hi) {
+                float *mine = lds + (b - lo);
+                double keep = (double)boot[s];
+                for (int i = m - 1; i >= 0; i--) {
+                    keep = returns_step(keep, gamma, mine[i]);
+                    mine[i] = (float)keep;
+                }
+            }
+            __syncthreads();
+            for (int i = threadIdx.x; i < hi - lo; i += RP_RET_SLOTS) out[lo + i] = lds[i];
+            return;
+        }
+    }
+    if (m <= 0) return;
+    double keep = (double)boot[s];
+#pragma unroll 4
+    for (int i = m - 1; i >= 0; i--) {
+        keep = returns_step(keep, gamma, rew[b + i]);
+        out[b + i] = (float)keep;
+    }
+}
+
 inline bool state_ok(const ReplayState *st) {
     return st && st->capacity > 0 && st->max_transitions > 0 && st->key_of_slot && st->sorted_keys && st->sorted_slot && st->row_of_slot && st->len &&
            st->flags && st->src_row && st->blk && st->counters && st->log_view && st->log_feat && st->log_act && st->log_rew && st->log_slot &&
@@ -358,6 +415,30 @@ int replay_pack(const ReplayState *st, int n_trans, void *out_view, void *out_fe
               st->view_row_bytes, st->feat_row_bytes, vec16(st->log_view, out_view, st->view_row_bytes), vec16(st->log_feat, out_feat, st->feat_row_bytes)};
     hipLaunchKernelGGL(k_replay_copy<false>, dim3(copy_blocks(n_trans)), dim3(RP_THREADS), 0, hs, c, (const int *)st->counters, 0, n_trans, (const int *)dst);
     return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+static int returns_launch(bool staged, const ReplayState *st, int n_slots, int n_trans, const int *base, const float *rew, const float *boot,
+                          double gamma, float *out_ret, void *stream) {
+    if (!state_ok(st) || n_slots < 0 || n_trans < 0 || n_slots > st->capacity || n_trans > st->max_transitions) return 1;
+    if (!base || !rew || !boot || !out_ret) return 1;
+    if (n_slots == 0 || n_trans == 0) return 0;
+    hipStream_t hs = (hipStream_t)stream;
+    StreamDevice on(hs);
+    if (!on.ok) return 2;
+    const dim3 grid((n_slots + RP_RET_SLOTS - 1) / RP_RET_SLOTS), block(RP_RET_SLOTS);
+    if (staged) hipLaunchKernelGGL(k_replay_returns<true>, grid, block, 0, hs, *st, n_slots, n_trans, base, rew, boot, gamma, out_ret);
+    else hipLaunchKernelGGL(k_replay_returns<false>, grid, block, 0, hs, *st, n_slots, n_trans, base, rew, boot, gamma, out_ret);
+    return hipGetLastError() == hipSuccess ? 0 : 3;
+}
+
+int replay_returns(const ReplayState *st, int n_slots, int n_trans, const int *base, const float *rew, const float *boot, double gamma,
+                   float *out_ret, void *stream) {
+    return returns_launch(true, st, n_slots, n_trans, base, rew, boot, gamma, out_ret, stream);
+}
+
+int replay_returns_direct(const ReplayState *st, int n_slots, int n_trans, const int *base, const float *rew, const float *boot, double gamma,
+                          float *out_ret, void *stream) {
+    return returns_launch(false, st, n_slots, n_trans, base, rew, boot, gamma, out_ret, stream);
 }
 
 }  // extern "C"

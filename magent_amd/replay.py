@@ -5,7 +5,7 @@ utility.EpisodesBuffer is a host object for one world: it reads the ids back eve
 what the batched acting path already has -- the packed observation, action and reward buffers, EnvBatch.agent_ids' packed ids and the
 packed_segments table --, keys agents by (world, id) as the segmented DRQN table does, and never waits for the host inside a round.  At
 the round's end it hands DeepQNetwork.train / DeepRecurrentQNetwork.train / AdvantageActorCritic.train what they already accept:
-packed() and episodes()."""
+packed() and episodes() -- and the A2C's discounted returns of the round, computed where it lies: last_rows() and returns()."""
 import ctypes
 import warnings
 
@@ -65,6 +65,12 @@ class DeviceEpisodesBuffer(object):
     transitions in time order -- as torch tensors on the recorder's device (actions int32, rewards float32, terminal bool, mask float32), or
     None when nothing was recorded.  It is the one place that reads a count back from the device.  Views come back in the format given;
     bf16 cells [.., H, W, 8] with view_channels=C as cells[..., :C].float() (exact), which a float32 replay memory takes.
+    last_rows() -> (slots, rows): int64 device tensors of the slots with at least one transition, ascending, and the packed row of each
+    one's last transition; None when nothing was recorded.  returns(bootstrap, gamma) -> float32 [transitions]: the discounted returns in
+    packed()'s order, keep = keep * gamma + reward from every episode's last row to its first, started from bootstrap[slot] (float32
+    [tracked] on the device; `tracked` is the count packed() read) -- in double, rounded once to float32: bit for bit what
+    AdvantageActorCritic.train computes on the host (include/magent_replay.h: replay_returns).  Both are valid until the next record_step,
+    close or reset, as packed() is.
     episodes() / buffer: the per-agent view, built on demand from the packed arrays; buffer is keyed by (segment, id), by id when every
     call had segments=None.  stats() reads back tracked agents, transitions and the overflow flag.  reset() empties the recorder.
 
@@ -248,8 +254,38 @@ class DeviceEpisodesBuffer(object):
                 if self.view_channels is not None and self.view_dtype == torch.bfloat16:
                     views = views[..., :self.view_channels].float()
                 self._packed = (views, feats, acts, rews, terminal, mask)
-                self._tracked = s["tracked"]
+            self._tracked = s["tracked"]
         return self._packed
+
+    @property
+    def tracked(self):
+        """the agents tracked, as packed() read the count: the length of returns()' bootstrap"""
+        self.packed()
+        return self._tracked
+
+    def last_rows(self):
+        if self.packed() is None:
+            return None
+        t = self._tracked
+        lens = self._len[:t].to(torch.int64)
+        slots = torch.nonzero(lens > 0).squeeze(1)
+        return slots, self._base[:t].to(torch.int64)[slots] + lens[slots] - 1
+
+    def returns(self, bootstrap, gamma):
+        if not getattr(self._lib, "has_replay_returns", False):
+            raise RuntimeError("the engine library has no replay_returns entry (include/magent_replay.h): rebuild it -- "
+                               "python -c 'import __graft_entry__ as g; g.build()'")
+        p = self.packed()
+        if p is None:
+            return None
+        t, n = self._tracked, int(p[3].shape[0])
+        if not (isinstance(bootstrap, torch.Tensor) and bootstrap.dtype == torch.float32 and tuple(bootstrap.shape) == (t,)
+                and bootstrap.device == self.device and bootstrap.is_contiguous()):
+            raise ValueError("bootstrap is a contiguous %s tensor %s on %s" % (torch.float32, (t,), self.device))
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        self._check(self._lib.replay_returns(self._st_ref, t, n, self._base.data_ptr(), p[3].data_ptr(), bootstrap.data_ptr(), float(gamma),
+                                             out.data_ptr(), self._stream()), "replay_returns")
+        return out
 
     @property
     def buffer(self):
